@@ -6,14 +6,17 @@ signature arithmetic + verdict scatter, then the verdict bytes copied to the
 host) over one batch of synthetic signed tokens already resident in HBM.
 
 Headline workload (BASELINE.json configs[1]): ES256, P-256 JWKS with 4 kids,
-1,048,576 tokens per GPU.  Second half of the metric: RS256 RSA-2048 on the same
+1,048,576 tokens per GPU; a plain run measures this and nothing else.  The rest
+rides behind --full.  Second half of the metric: RS256 RSA-2048 on the same
 batch size (reported under "rs256").  The other BASELINE configs are reported
 under "configs" (per-GPU share of each, same timing rules), the end-to-end
 Validator.ValidateBatch rate (host parse + GPU + claims) under "e2e".  Tokens
 are signed by OpenSSL (tools/tokgen) from a unique pool replicated to the batch
 size; verdicts are never cached, and every line checks its accept count.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W]     the headline alone: set-up, warm-up, K timed steps
+    python bench.py --full ...                          every other leg as well (RS256, configs, e2e, CPU baselines)
+    python bench.py --dump-outputs DIR ...              the last timed step's verdicts as DIR/verdicts.npy
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, weak scaling)
 """
 import argparse
@@ -207,10 +210,13 @@ def ensure_tokgen():
         subprocess.run(["make", "-s", "-C", os.path.dirname(TOKGEN)], check=True)
 
 
-def gen_tokens(alg, count, keypaths, threads, tag, kid_base=0):
+def gen_tokens(alg, count, keypaths, threads, tag, kid_base=0, salt=""):
+    """`count` signed tokens from tools/tokgen, the same bytes on every call
+    with the same arguments (PS* apart: random salts); `salt` picks another
+    set of ES* signatures over the same signing inputs."""
     ensure_tokgen()
     out = os.path.join("/tmp", f"capjwt_{tag}_{alg}_{count}_{kid_base}_{os.getpid()}.txt")
-    env = dict(os.environ, TOKGEN_KID_BASE=str(kid_base))
+    env = dict(os.environ, TOKGEN_KID_BASE=str(kid_base), TOKGEN_NONCE_SALT=salt)
     subprocess.run([TOKGEN, alg, str(count), str(threads), out] + list(keypaths), check=True, env=env)
     with open(out, "rb") as f:
         toks = f.read().split(b"\n")[:count]
@@ -325,6 +331,9 @@ def measure(ctx, arena, toks, steps, warmup, dist, second=None):
     for bb, _, _ in batches:
         bb.sync()
     elapsed = time.perf_counter() - t0
+    # what the last timed step handed back: its verdict bytes (--dump-outputs)
+    global LAST_VERDICTS
+    LAST_VERDICTS = np.frombuffer(batches[(steps - 1) % len(batches)][1].bytes(), dtype=np.uint8)
     for bb, pb, acc in batches[:min(steps, len(batches))]:
         if int(np.frombuffer(pb.bytes(), dtype=np.uint8).sum()) != acc:
             raise RuntimeError("verdicts changed between runs")
@@ -351,6 +360,25 @@ def measure(ctx, arena, toks, steps, warmup, dist, second=None):
 LAST_WINDOW = None
 LAST_SYNC_MS = None
 LAST_ACCEPTED2 = None       # accepted count of measure()'s second staged batch
+LAST_VERDICTS = None        # verdict bytes of measure()'s last timed step
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: write {name: array} as `dirpath`/<name>.npy in float32
+    (float64 arrays stay float64).  An output over the 64 MB the files may
+    take in all is cut to a fixed, seeded sample of its elements, in order."""
+    os.makedirs(dirpath, exist_ok=True)
+    room = DUMP_MAX_BYTES // max(1, len(arrays)) - 4096          # .npy header
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32).reshape(-1)
+        if a.nbytes > room:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, room // a.itemsize, replace=False))
+            a = a[keep]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def h2d_bandwidth(nbytes, iters=5):
@@ -1304,6 +1332,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--tokens", type=int, default=1 << 20, help="tokens per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure every other leg: the pinned-host (PCIe) pass, "
+                         "the default-budget and replicated-pool A/B lines, RS256, the other BASELINE configs, the "
+                         "end-to-end, single-call and multi-device legs and the CPU baselines (the --no-* options "
+                         "drop legs from it); without it the run sets up, warms up, times the ES256 steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (its verdict bytes, one per token) as "
+                         "DIR/verdicts.npy, float32; the tokens are the same bytes on every run with the same arguments")
     ap.add_argument("--c5-chunk", type=int, default=625000,
                     help="configs[4] resident chunk (tokens per step; default: half of the GPU's 1.25M share, so the "
                          "two alternating staged chunks cover the whole share)")
@@ -1339,6 +1376,10 @@ def main():
     args = ap.parse_args()
     if args.e2e_child:
         return e2e_child_main(args.e2e_child, args.tokens)
+    if not (args.full or args.configs_only):
+        # a plain run: the headline's set-up, warm-up and timed steps only
+        args.no_ab = args.no_rs256 = args.no_configs = args.no_e2e = args.no_cpu = True
+        args.md_devices = "none"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1395,13 +1436,15 @@ def main():
     pool = gen_tokens("ES256", npool, golden_keypaths(kids), host_threads, f"r{rank}")
     arena, toks = pack(pool, [ALG_IDS["ES256"]] * npool, np.arange(npool) % len(kids), args.tokens)
     # the second staged batch of measure(): another npool unique tokens
-    pool2 = gen_tokens("ES256", npool, golden_keypaths(kids), host_threads, f"r{rank}b")
+    pool2 = gen_tokens("ES256", npool, golden_keypaths(kids), host_threads, f"r{rank}b", salt="b")
     second = pack(pool2, [ALG_IDS["ES256"]] * npool, np.arange(npool) % len(kids), args.tokens)
     del pool2
     el, acc, kms, _ = measure(ctx, arena, toks, args.steps, args.warmup, dist, second=second)
     acc2 = LAST_ACCEPTED2
     es_window = LAST_WINDOW
     del second
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verdicts" if rank == 0 else f"verdicts_rank{rank}": LAST_VERDICTS})
     ntok = len(toks)
     value = world * ntok * args.steps / el
     ms_step = el * 1000.0 / args.steps
@@ -1450,7 +1493,7 @@ def main():
     }
     if acc != ntok or acc2 not in (None, ntok):
         result["error"] = f"only {acc}/{ntok} (second batch {acc2}) valid tokens accepted"
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         result["pcie"] = measure_pcie(ctx, arena, toks)
     # the same batch at the library's default table budget (what a caller gets
     # without jg_set_table_budget): the 4 kids' key tables at W = 24

@@ -115,6 +115,34 @@ def test_compact_line_fits_and_keeps_the_contract_keys(tmp_path):
     assert line["multi_device"]["verify_batch"] == 5e8
 
 
+def test_dump_outputs_writes_float_npy_within_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    v = (np.arange(1000) % 7 == 0).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "o"), {"verdicts": v})
+    got = np.load(tmp_path / "o" / "verdicts.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    # an output over the limit: the same seeded sample, in order, on every call
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 400)
+    w = np.arange(1000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"w": w})
+    bench.dump_outputs(str(tmp_path / "b"), {"w": w})
+    a, b = np.load(tmp_path / "a" / "w.npy"), np.load(tmp_path / "b" / "w.npy")
+    assert a.dtype == np.float64 and a.size == 50 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and os.path.getsize(tmp_path / "a" / "w.npy") <= 4096 + 400
+
+
+def test_plain_run_skips_what_full_adds():
+    """Every leg beside the headline sits behind --full (or its own mode,
+    --configs-only): main() turns each of them off for a plain run."""
+    bsrc = open(os.path.join(ROOT, "bench.py")).read()
+    gate = bsrc[bsrc.index("if not (args.full or args.configs_only):"):]
+    gate = gate[:gate.index("world = ")]
+    for flag in ("no_ab", "no_rs256", "no_configs", "no_e2e", "no_cpu"):
+        assert f"args.{flag}" in gate, flag
+    assert 'args.md_devices = "none"' in gate
+    assert 'if args.full and rank == 0 and world == 1:\n        result["pcie"]' in bsrc
+
+
 def test_emit_line_writes_the_detail_file(tmp_path, capsys):
     import json
     full = _full_result()

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 TAG=${1:-r03}
 O=gpurun_out/$TAG
 mkdir -p "$O"
-ARGS="--steps 4 --warmup 1 --no-cpu --no-e2e --no-configs --no-ab"
+ARGS="--full --steps 4 --warmup 1 --no-cpu --no-e2e --no-configs --no-ab"
 echo "[1/5] kernel trace $(date +%T)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/kt" -o kt --output-format csv -- python3 bench.py $ARGS > "$O/kt.json" 2> "$O/kt.err" || { echo KT_FAIL; tail -20 "$O/kt.err"; exit 1; }
 echo "[2/5] FETCH_SIZE $(date +%T)"

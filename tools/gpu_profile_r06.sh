@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 TAG=${1:-r06}
 O=gpurun_out/$TAG
 mkdir -p "$O"
-ARGS="--steps 4 --warmup 1 --no-cpu --no-e2e --no-configs --no-ab --md-devices none"
+ARGS="--full --steps 4 --warmup 1 --no-cpu --no-e2e --no-configs --no-ab --md-devices none"
 # SKIP_HEAD=1: only the calibration and configs passes (a rerun after the headline passes)
 run() {  # name, rocprof args...
   local n=$1; shift

@@ -8,10 +8,13 @@
  * Token i uses key i % nkeys; header {"alg":ALG,"kid":"kid-KK","typ":"JWT"},
  * payload shaped like cap's testJWTClaims (jwt/keyset_test.go:666-677) with
  * jti = i.  One token per line.  PS* use salt length = hash length (go-jose).
+ * RS*, ES* and EdDSA tokens are the same bytes on every run (ES* nonces are
+ * derived, see es_sign); PS* salts are random.
  */
 #include <openssl/bn.h>
 #include <openssl/ecdsa.h>
 #include <openssl/evp.h>
+#include <openssl/hmac.h>
 #include <openssl/pem.h>
 #include <openssl/rsa.h>
 #include <pthread.h>
@@ -59,11 +62,53 @@ static int es_size(const char* alg) {
   return !strcmp(alg, "ES256") ? 32 : !strcmp(alg, "ES384") ? 48 : 66;
 }
 
+/* ES*: r || s with a nonce derived from the key, the digest and `salt`
+ * (HMAC-SHA512 in counter mode, reduced mod n - 1, plus 1), so a run's tokens
+ * are the same bytes every time -- two builds of the library can be compared
+ * verdict for verdict on identical inputs.  TOKGEN_NONCE_SALT=text gives
+ * another set of signatures over the same signing inputs.  Test input only:
+ * not RFC 6979, not constant time. */
+static void es_sign(EC_KEY* ec, const EVP_MD* md, const char* msg, size_t mlen, int sz, const char* salt,
+                    unsigned char* raw) {
+  unsigned char dg[EVP_MAX_MD_SIZE], dk[200], kb[128], mac[64], in[EVP_MAX_MD_SIZE + 1 + 64];
+  const size_t sn = strnlen(salt, 64);
+  unsigned dl = 0, ml = 0;
+  if (EVP_Digest(msg, mlen, dg, &dl, md, NULL) != 1) { fprintf(stderr, "es digest\n"); exit(2); }
+  const EC_GROUP* g = EC_KEY_get0_group(ec);
+  const int dn = BN_bn2binpad(EC_KEY_get0_private_key(ec), dk, sz);
+  memcpy(in, dg, dl);
+  memcpy(in + dl + 1, salt, sn);
+  for (int c = 0; c < 2; ++c) {
+    in[dl] = (unsigned char)c;
+    if (dn != sz || !HMAC(EVP_sha512(), dk, dn, in, dl + 1 + sn, mac, &ml) || ml != 64) { fprintf(stderr, "es nonce\n"); exit(2); }
+    memcpy(kb + 64 * c, mac, 64);
+  }
+  BN_CTX* bc = BN_CTX_new();
+  BIGNUM *k = BN_bin2bn(kb, sizeof kb, NULL), *n1 = BN_dup(EC_GROUP_get0_order(g)), *r = BN_new(), *kinv = BN_new();
+  EC_POINT* pt = EC_POINT_new(g);
+  BN_sub_word(n1, 1);
+  if (!BN_mod(k, k, n1, bc) || !BN_add_word(k, 1) || EC_POINT_mul(g, pt, k, NULL, NULL, bc) != 1 ||
+      EC_POINT_get_affine_coordinates(g, pt, r, NULL, bc) != 1 || !BN_mod(r, r, EC_GROUP_get0_order(g), bc) ||
+      BN_is_zero(r) || !BN_mod_inverse(kinv, k, EC_GROUP_get0_order(g), bc)) { fprintf(stderr, "es point\n"); exit(2); }
+  ECDSA_SIG* es = ECDSA_do_sign_ex(dg, (int)dl, kinv, r, ec);
+  if (!es) { fprintf(stderr, "es sign\n"); exit(2); }
+  const BIGNUM *sr, *ss;
+  ECDSA_SIG_get0(es, &sr, &ss);
+  BN_bn2binpad(sr, raw, sz);
+  BN_bn2binpad(ss, raw + sz, sz);
+  ECDSA_SIG_free(es);
+  EC_POINT_free(pt);
+  BN_free(k); BN_free(n1); BN_free(r); BN_free(kinv);
+  BN_CTX_free(bc);
+}
+
 static void* worker(void* arg) {
   job* j = (job*)arg;
   /* TOKGEN_PAD=n: a "pad" claim of n 'x' bytes (long signing inputs) */
   const char* pe = getenv("TOKGEN_PAD");
   const size_t padn = pe ? (size_t)atol(pe) : 0;
+  const char* salt = getenv("TOKGEN_NONCE_SALT");
+  if (!salt) salt = "";
   char hdr[256], hb[512], sb[1500];
   char* pay = malloc(512 + padn);
   char* pb = malloc(2 * (512 + padn) + 8);
@@ -71,6 +116,7 @@ static void* worker(void* arg) {
   memset(padv, 'x', padn);
   padv[padn] = 0;
   unsigned char sig[1024], raw[200];
+  EC_KEY** ecs = calloc((size_t)j->nkeys, sizeof(EC_KEY*));     /* this thread's copies, made at first use */
   for (long i = j->lo; i < j->hi; ++i) {
     const int k = (int)(i % j->nkeys);
     snprintf(hdr, sizeof hdr, "{\"alg\":\"%s\",\"kid\":\"kid-%02d\",\"typ\":\"JWT\"}", j->alg, j->kid_base + k);
@@ -88,30 +134,26 @@ static void* worker(void* arg) {
     char* si = malloc(hl + pl + 2);
     memcpy(si, hb, hl); si[hl] = '.'; memcpy(si + hl + 1, pb, pl); si[hl + pl + 1] = 0;
     const size_t slen_in = hl + pl + 1;
-    EVP_MD_CTX* mc = EVP_MD_CTX_new();
-    EVP_PKEY_CTX* pc = NULL;
-    size_t sl = sizeof sig;
-    if (EVP_DigestSignInit(mc, &pc, alg_md(j->alg), NULL, j->keys[k]) != 1) { fprintf(stderr, "init\n"); exit(2); }
-    if (j->alg[0] == 'P') {
-      EVP_PKEY_CTX_set_rsa_padding(pc, RSA_PKCS1_PSS_PADDING);
-      EVP_PKEY_CTX_set_rsa_pss_saltlen(pc, RSA_PSS_SALTLEN_DIGEST);
-    }
-    if (EVP_DigestSign(mc, sig, &sl, (const unsigned char*)si, slen_in) != 1) { fprintf(stderr, "sign\n"); exit(2); }
-    EVP_MD_CTX_free(mc);
     const unsigned char* s = sig;
-    size_t n = sl;
-    if (j->alg[0] == 'E' && j->alg[1] == 'S') {             /* DER -> r || s */
-      const unsigned char* p = sig;
-      ECDSA_SIG* es = d2i_ECDSA_SIG(NULL, &p, (long)sl);
-      const BIGNUM *r, *ss;
-      ECDSA_SIG_get0(es, &r, &ss);
+    size_t n;
+    if (j->alg[0] == 'E' && j->alg[1] == 'S') {             /* r || s, nonce from key and digest */
       const int sz = es_size(j->alg);
-      memset(raw, 0, sizeof raw);
-      BN_bn2binpad(r, raw, sz);
-      BN_bn2binpad(ss, raw + sz, sz);
-      ECDSA_SIG_free(es);
+      if (!ecs[k] && !(ecs[k] = EVP_PKEY_get1_EC_KEY(j->keys[k]))) { fprintf(stderr, "not an EC key\n"); exit(2); }
+      es_sign(ecs[k], alg_md(j->alg), si, slen_in, sz, salt, raw);
       s = raw;
       n = 2 * (size_t)sz;
+    } else {
+      EVP_MD_CTX* mc = EVP_MD_CTX_new();
+      EVP_PKEY_CTX* pc = NULL;
+      size_t sl = sizeof sig;
+      if (EVP_DigestSignInit(mc, &pc, alg_md(j->alg), NULL, j->keys[k]) != 1) { fprintf(stderr, "init\n"); exit(2); }
+      if (j->alg[0] == 'P') {
+        EVP_PKEY_CTX_set_rsa_padding(pc, RSA_PKCS1_PSS_PADDING);
+        EVP_PKEY_CTX_set_rsa_pss_saltlen(pc, RSA_PSS_SALTLEN_DIGEST);
+      }
+      if (EVP_DigestSign(mc, sig, &sl, (const unsigned char*)si, slen_in) != 1) { fprintf(stderr, "sign\n"); exit(2); }
+      EVP_MD_CTX_free(mc);
+      n = sl;
     }
     size_t bl = b64url(s, n, sb);
     char* tok = malloc(slen_in + bl + 2);
@@ -122,6 +164,8 @@ static void* worker(void* arg) {
   free(pay);
   free(pb);
   free(padv);
+  for (int k = 0; k < j->nkeys; ++k) EC_KEY_free(ecs[k]);
+  free(ecs);
   return NULL;
 }
 
