@@ -15,8 +15,9 @@ struct EcArgs {
   uint8_t* status;
   uint8_t* verdict_pad;
   uint32_t* digs;             // signed digit rows: u1 windows (generator) then u2 windows (key)
-  uint32_t* u1w;              // u1, u2 canonical 28-bit limb rows (exact path)
-  uint32_t* u2w;
+  uint32_t* u1w;              // scratch of the batched scalar stage, ec_limbs rows each: the prefix
+  uint32_t* u2w;              // products c_j (u1w) and s_j in Montgomery form (u2w); k_ec_exact
+                              // recomputes u1 and u2 itself and reads neither
   const uint32_t* gtab;       // comb table of the generator for this curve
   int32_t* exc_list;          // padded indices needing the exact path
   uint32_t* exc_count;

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "ecdsa.hpp"
+#include "inv_shape.hpp"
 #include "mp.hpp"
 #include "tables.hpp"
 
@@ -1222,20 +1223,14 @@ void launch_chain(const EcArgs& a, hipStream_t s, const Marker& mk) {
     mk("exact");
     return;
   }
-  // tokens per thread for the batched inversion: keep >= ~8 waves per CU
-  // (profiles/r04_s3/scalar_occupancy_ab.json: more waves, fewer tokens per
-  // inversion, measured 12-26 % slower)
+  // tokens per thread for the batched inversion, and one wave per block for a
+  // small launch (inv_shape.hpp)
   const int64_t n = a.end - a.begin;
-  constexpr int wpc = 8;
-  int B = (int)std::min<int64_t>(16, std::max<int64_t>(1, n / (256 * wpc * WAVE)));
-  const int64_t S = (n + B - 1) / B;
-  if (n <= EC_SCALAR_SOLO_MAX) {
-    // a small launch: one inversion per wave, no block barrier (the shared
-    // inversion saves inversions only when the chip is full)
-    hipLaunchKernelGGL((k_ec_scalar_batch<CV, 1>), dim3((unsigned)((S + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, a, B);
+  const InvShape sh = inv_shape(n, EC_SCALAR_WPB, EC_SCALAR_SOLO_MAX);
+  if (sh.wpb == 1) {
+    hipLaunchKernelGGL((k_ec_scalar_batch<CV, 1>), dim3(sh.grid), dim3(WAVE), 0, s, a, sh.B);
   } else {
-    constexpr int TPB = WAVE * EC_SCALAR_WPB;
-    hipLaunchKernelGGL(k_ec_scalar_batch<CV>, dim3((unsigned)((S + TPB - 1) / TPB)), dim3(TPB), 0, s, a, B);
+    hipLaunchKernelGGL(k_ec_scalar_batch<CV>, dim3(sh.grid), dim3(WAVE * EC_SCALAR_WPB), 0, s, a, sh.B);
   }
   mk("scalar");
   // a launch of fewer waves than ~2 per SIMD runs its tokens S lanes each

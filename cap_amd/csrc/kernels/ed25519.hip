@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "ed25519.hpp"
 #include "fe25519.hpp"
+#include "inv_shape.hpp"
 #include "mp.hpp"
 #include "tables.hpp"
 #include "small_common.hpp"
@@ -39,6 +40,31 @@ __device__ __forceinline__ bool lt_limbs(const uint32_t* a, const uint32_t* b) {
     gt |= und & (a[j] > b[j]);
   }
   return lt;
+}
+
+// k = H mod L, canonical 28-bit limbs; hw: the 512-bit H as 16 little-endian
+// words (hw[0] = digest bytes 0..3, byte 0 lowest)
+__device__ __forceinline__ void ed_k_mod_l(uint32_t* k, const uint32_t* hw) {
+  uint32_t hl[2 * L];
+  mp::words_to_limbs<2 * L, 16>(hl, hw);
+  uint64_t tt[2 * L];
+#pragma unroll
+  for (int j = 0; j < 2 * L; ++j) tt[j] = hl[j];
+  uint32_t kr[L], rr[L];
+  mp::mont_reduce<Fl>(kr, tt);            // H / R mod L
+  mp::set_const<Fl>(rr, Fl::RR);
+  mp::mul<Fl>(k, kr, rr);                 // H mod L (< 2L)
+  mp::csub<Fl>(k);
+}
+
+// S of a signature (sw: sig[32..64) as 8 little-endian words) as limbs s;
+// true iff sig[63] & 0xE0 == 0 and S < L (R24)
+__device__ __forceinline__ bool ed_s_ok(uint32_t* s, const uint32_t* sw) {
+  const bool top = (sw[7] & 0xE0000000u) == 0;
+  mp::words_to_limbs<L, 8>(s, sw);
+  uint32_t lord[L];
+  mp::set_const<Fl>(lord, Fl::M);
+  return top && lt_limbs(s, lord);
 }
 
 struct EPt { uint32_t X[L], Y[L], Z[L], T[L]; };
@@ -222,29 +248,18 @@ __device__ __forceinline__ void ed_point_body(const EdArgs& a) {
   uint32_t sw[8], s[L];
 #pragma unroll
   for (int q = 0; q < 8; ++q) sw[q] = a.sigw[(int64_t)(8 + q) * np + p];
-  ok = ok && (sw[7] & 0xE0000000u) == 0;
-  mp::words_to_limbs<L, 8>(s, sw);
-  uint32_t lord[L];
-  mp::set_const<Fl>(lord, Fl::M);
-  ok = ok && lt_limbs(s, lord);
+  const bool sok = ed_s_ok(s, sw);
+  ok = ok && sok;
   // k = H mod L  (H little-endian, 512 bits)
   uint32_t k[L];
   {
-    uint32_t hw[16], hl[2 * L];
+    uint32_t hw[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const uint32_t x = a.dig[(int64_t)q * np + p];
       hw[q] = (x >> 24) | ((x >> 8) & 0xff00u) | ((x << 8) & 0xff0000u) | (x << 24);
     }
-    mp::words_to_limbs<2 * L, 16>(hl, hw);
-    uint64_t tt[2 * L];
-#pragma unroll
-    for (int j = 0; j < 2 * L; ++j) tt[j] = hl[j];
-    uint32_t kr[L], rr[L];
-    mp::mont_reduce<Fl>(kr, tt);            // H / R mod L
-    mp::set_const<Fl>(rr, Fl::RR);
-    mp::mul<Fl>(k, kr, rr);                 // H mod L (< 2L)
-    mp::csub<Fl>(k);
+    ed_k_mod_l(k, hw);
   }
   constexpr int NB = ed_windows(true), NA = ed_windows_w(WA), NW = NB > NA ? NB : NA;
   // the signed digits of S (B windows) and k (-A windows) wait in LDS, one row
@@ -348,30 +363,19 @@ __global__ void __launch_bounds__(64) JG_ED_POINT_ATTR k_ed_point_split(EdArgs a
     uint32_t sw[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) sw[q] = live ? a.sigw[(int64_t)(8 + q) * np + p] : 0u;
-    ok = ok && (sw[7] & 0xE0000000u) == 0;
-    mp::words_to_limbs<L, 8>(sc, sw);
-    uint32_t lord[L];
-    mp::set_const<Fl>(lord, Fl::M);
-    ok = ok && lt_limbs(sc, lord);
+    const bool sok = ed_s_ok(sc, sw);
+    ok = ok && sok;
     recode<ed_comb_w(true), NB>(dg + lane, sc, WAVE);
     for (int w = NB; w < NW; ++w) dg[w * WAVE + lane] = 0;
   } else {
     // k = H mod L  (H little-endian, 512 bits)
-    uint32_t hw[16], hl[2 * L];
+    uint32_t hw[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const uint32_t x = live ? a.dig[(int64_t)q * np + p] : 0u;
       hw[q] = (x >> 24) | ((x >> 8) & 0xff00u) | ((x << 8) & 0xff0000u) | (x << 24);
     }
-    mp::words_to_limbs<2 * L, 16>(hl, hw);
-    uint64_t tt[2 * L];
-#pragma unroll
-    for (int j = 0; j < 2 * L; ++j) tt[j] = hl[j];
-    uint32_t kr[L], rr[L];
-    mp::mont_reduce<Fl>(kr, tt);
-    mp::set_const<Fl>(rr, Fl::RR);
-    mp::mul<Fl>(sc, kr, rr);
-    mp::csub<Fl>(sc);
+    ed_k_mod_l(sc, hw);
     recode<WA, NA>(dg + lane, sc, WAVE);
     for (int w = NA; w < NW; ++w) dg[w * WAVE + lane] = 0;
   }
@@ -607,33 +611,23 @@ __global__ void __launch_bounds__(SM_THREADS) k_ed_small(EdSmallArgs a) {
       sha2::sha512_compress(h, w);
     }
     // k = H mod L (H little-endian, 512 bits; k_ed_point's reduction)
-    uint32_t hw[16], hl[2 * L];
+    uint32_t hw[16], k[L];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       hw[2 * q] = sha2::bswap32((uint32_t)(h[q] >> 32));
       hw[2 * q + 1] = sha2::bswap32((uint32_t)h[q]);
     }
-    mp::words_to_limbs<2 * L, 16>(hl, hw);
-    uint64_t tt[2 * L];
-#pragma unroll
-    for (int j = 0; j < 2 * L; ++j) tt[j] = hl[j];
-    uint32_t kr[L], rr[L], k[L];
-    mp::mont_reduce<Fl>(kr, tt);
-    mp::set_const<Fl>(rr, Fl::RR);
-    mp::mul<Fl>(k, kr, rr);
-    mp::csub<Fl>(k);
+    ed_k_mod_l(k, hw);
     recode<WA, NA>(dg + NB, k);
   }
   if (ok0 && wave == 1 && lane == 0) {
     // S: canonical (S < L) and sig[63] & 0xE0 == 0 (R24)
-    uint32_t sw[8], sl[L], lord[L];
+    uint32_t sw[8], sl[L];
 #pragma unroll
     for (int q = 0; q < 8; ++q)
       sw[q] = (uint32_t)sig_b[32 + 4 * q] | ((uint32_t)sig_b[33 + 4 * q] << 8) | ((uint32_t)sig_b[34 + 4 * q] << 16) |
               ((uint32_t)sig_b[35 + 4 * q] << 24);
-    mp::words_to_limbs<L, 8>(sl, sw);
-    mp::set_const<Fl>(lord, Fl::M);
-    const bool sok = (sw[7] & 0xE0000000u) == 0 && lt_limbs(sl, lord);
+    const bool sok = ed_s_ok(sl, sw);
     recode<ed_comb_w(true), NB>(dg, sl);
     flag[1] = sok ? 1 : 0;
   }
@@ -929,12 +923,10 @@ void launch_ed(const EdArgs& a, hipStream_t s, const Marker& mk) {
   }
   }
   mk("point");
-  // tokens per thread for the batched inversion: keep >= ~8 waves per CU
-  const int64_t n = a.end - a.begin;
-  const int B = (int)std::min<int64_t>(16, std::max<int64_t>(1, n / (256 * 8 * WAVE)));
-  const int64_t S = (n + B - 1) / B;
-  constexpr int TPB = WAVE * ED_FINISH_WPB;
-  hipLaunchKernelGGL(k_ed_finish, dim3((unsigned)((S + TPB - 1) / TPB)), dim3(TPB), 0, s, a, B);
+  // tokens per thread for the batched inversion (inv_shape.hpp; every launch
+  // runs ED_FINISH_WPB waves per block)
+  const InvShape sh = inv_shape(a.end - a.begin, ED_FINISH_WPB, 0);
+  hipLaunchKernelGGL(k_ed_finish, dim3(sh.grid), dim3(WAVE * ED_FINISH_WPB), 0, s, a, sh.B);
   mk("finish");
 }
 

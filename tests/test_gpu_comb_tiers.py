@@ -170,6 +170,64 @@ def test_mixed_width_class_with_exceptions_in_both_runs():
         ctx.close()
 
 
+def _padded(toks):
+    """padded jobs of a one-class batch: every key's run filled to whole waves (kernels/common.hpp)"""
+    per_key = {}
+    for t in toks:
+        per_key[t["key"]] = per_key.get(t["key"], 0) + 1
+    return sum(-(-c // 64) * 64 for c in per_key.values())
+
+
+def _resident_two_per_thread(keys, toks, table, wq):
+    """one resident launch of 262,144 .. 393,215 padded jobs: the batched-
+    inversion stage runs two tokens per thread (kernels/inv_shape.hpp;
+    test_gpu_inv_shape.py pins the table)"""
+    import bench
+    from cap_amd import _lib
+    assert 262144 <= _padded(toks) < 393216
+    kid_index = {k["kid"]: i for i, k in enumerate(keys)}
+    ctx = _lib.Context()
+    try:
+        ctx.set_table_budget(len(keys) * bench.table_bytes(table, wq))
+        ctx.load_keys([H.abi_key(k) for k in keys])
+        assert ctx.table_widths() == [wq] * len(keys)
+        arena, slots = H.jobs_from_tokens(toks, kid_index)
+        assert None not in slots
+        b = ctx.stage(arena)
+        res = b.run(want_verdicts=True)
+        b.free()
+        bad = [t["name"] for t, sl in zip(toks, slots) if res[sl] != t["verdict"]]
+        assert not bad, (len(bad), bad[:10])
+    finally:
+        ctx.close()
+
+
+def test_ecdsa_p256_w20_launch_with_two_tokens_per_thread():
+    """The W = 20 tier's tokens and the rejecting P-256 tokens of ec_edge.json
+    (exceptional sums, x(R) >= n with r + 1), tiled to just over 262,144 padded
+    jobs and run as a resident batch: one class launch, large enough for
+    launch_chain to give k_ec_scalar_batch two tokens per thread (every smaller
+    launch of the suite runs one).  Every verdict equals the fixture's."""
+    s = next(x for x in fixtures()["ec"] if x["crv"] == "P-256" and x["wq"] == 20)
+    edge = json.load(open(os.path.join(H.ROOT, "tests", "golden", "ec_edge.json")))
+    ekeys = {k["kid"]: k for k in edge["keys"]}
+    rej = [t for t in edge["tokens"] if t["verdict"] == 0 and ekeys.get(t["key"], {}).get("crv") == "P-256"]
+    assert len(rej) >= 4
+    keys = s["keys"] + [ekeys[k] for k in sorted({t["key"] for t in rej})]
+    base = s["tokens"] + rej
+    toks = base * (263000 // len(base) + 1)
+    _resident_two_per_thread(keys, toks, "p256", 20)
+
+
+def test_ed25519_w16_launch_with_two_tokens_per_thread():
+    """The Ed25519 edge tokens (half of them rejecting copies) tiled to just
+    over 262,144 padded jobs, resident, at W = 16: launch_ed gives k_ed_finish
+    two tokens per thread."""
+    s = fixtures()["ed25519"]
+    toks = s["tokens"] * (262144 // len(s["tokens"]) + 1)
+    _resident_two_per_thread(s["keys"], toks, "ed25519", 16)
+
+
 @pytest.mark.parametrize("n", [20000, 140000])
 @pytest.mark.parametrize("wa", [24, 20, 16])
 def test_ed25519_comb_tier_large_launch(wa, n):
