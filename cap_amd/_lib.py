@@ -24,7 +24,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_submit", "jg_wait", "jg_set_chunk", "jg_set_zero_copy", "jg_set_table_budget", "jg_keys_wait_tables",
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
-           "jg_debug_small_path"]
+           "jg_debug_small_path", "jg_claims_scan"]
 
 
 class JgKey(ctypes.Structure):
@@ -40,6 +40,36 @@ class JgTok(ctypes.Structure):
 
 
 assert ctypes.sizeof(JgTok) == 24
+
+MAX_AUD = 16                       # JG_MAX_AUD
+# jg_claim_code
+CL_OK, CL_NO_TIME, CL_ISS, CL_SUB, CL_JTI, CL_AUD, CL_NBF, CL_EXP, CL_IAT, CL_HOST = range(10)
+# the string Validator.Validate gives for each code (jwt/jwt.go:117-199)
+CLAIM_ERRORS = {
+    CL_OK: None,
+    CL_NO_TIME: "no issued at (iat), not before (nbf), or expiration time (exp) claims in token",
+    CL_ISS: "invalid issuer (iss) claim",
+    CL_SUB: "invalid subject (sub) claim",
+    CL_JTI: "invalid ID (jti) claim",
+    CL_AUD: "invalid audience (aud) claim: audience claim does not match any expected audience",
+    CL_NBF: "invalid not before (nbf) claim: token not yet valid",
+    CL_EXP: "invalid expiration time (exp) claim: token is expired",
+    CL_IAT: "invalid issued at (iat) claim: token issued in the future",
+}
+
+
+class JgCJob(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class JgExpect(ctypes.Structure):
+    _fields_ = [("strs", ctypes.c_void_p), ("iss_len", ctypes.c_uint32), ("sub_len", ctypes.c_uint32),
+                ("jti_len", ctypes.c_uint32), ("naud", ctypes.c_uint32), ("aud_len", ctypes.c_uint32 * MAX_AUD),
+                ("now_sec", ctypes.c_int64), ("now_nsec", ctypes.c_uint32), ("pad_", ctypes.c_uint32),
+                ("skew_ns", ctypes.c_int64), ("exp_leeway_s", ctypes.c_int64), ("nbf_leeway_s", ctypes.c_int64)]
+
+
+assert ctypes.sizeof(JgCJob) == 16
 
 _lib = None
 
@@ -80,6 +110,7 @@ def lib():
         L.jg_set_zero_copy.argtypes = [vp, ctypes.c_int, sz]
         L.jg_set_table_budget.argtypes = [vp, ctypes.c_uint64]
         L.jg_hash_batch.argtypes = [vp, vp, sz, vp, sz, vp]
+        L.jg_claims_scan.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect), vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -256,6 +287,35 @@ class Context:
         if rc != 0:
             raise JgError(f"jg_verify_batch rc={rc}: {self.error()}")
         return bytes(out[:n])
+
+    def claims_scan(self, arena_bytes, spans, expect, flags=0):
+        """jg_claims_scan: one jg_claim_code byte per (off, len) span of base64url
+        payload segment in `arena_bytes`.  `expect`: a dict with issuer, subject,
+        id (bytes), audiences (list of bytes), now_sec, now_nsec, skew_ns,
+        exp_leeway_s, nbf_leeway_s -- already resolved (see include/jg.h)."""
+        n = len(spans)
+        jobs = (JgCJob * max(1, n))()
+        for i, (off, ln) in enumerate(spans):
+            jobs[i].off, jobs[i].len, jobs[i].flags = off, ln, flags
+        auds = [bytes(a) for a in expect.get("audiences", [])]
+        strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
+        blob = b"".join(strs + auds)
+        e = JgExpect()
+        keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+        e.strs = ctypes.cast(keep, ctypes.c_void_p)
+        e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
+        e.naud = len(auds)
+        for k, a in enumerate(auds[:MAX_AUD]):
+            e.aud_len[k] = len(a)
+        e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
+        e.skew_ns = int(expect["skew_ns"])
+        e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
+        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
+        buf = bytes(arena_bytes) or b"\0"
+        rc = lib().jg_claims_scan(self.h, buf, len(arena_bytes), jobs, n, ctypes.byref(e), out)
+        if rc != 0:
+            raise JgError(f"jg_claims_scan rc={rc}: {self.error()}")
+        return out.raw[:n]
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

@@ -625,6 +625,12 @@ struct Verified {
   uint64_t dev_seen = 0;
   bool dev_failed = false;
   std::string miss_err;              // JWKS: the error of a parsed token no key verified
+  // during the Overlap call only: the pinned arena the device verifies from
+  // and its jobs (token t's entry starts at jobs[t.job0].off) -- CheckBatch
+  // scans the payload segments in place there
+  const uint8_t* arena = nullptr;
+  size_t arena_len = 0;
+  const jg_tok* jobs = nullptr;
 };
 
 namespace {
@@ -715,7 +721,18 @@ void gpu_verify(Engine& eng, const std::vector<std::string_view>& tokens, Verifi
     eng.verify(arena.get(), arena_len, jobs.get(), total_jobs, verdict.get(), [&] {
       release_keys();
       if (overlap) {
-        (*overlap)(*V);
+        V->arena = arena.get();
+        V->arena_len = arena_len;
+        V->jobs = jobs.get();
+        try {
+          (*overlap)(*V);
+        } catch (...) {
+          V->arena = nullptr;
+          V->jobs = nullptr;
+          throw;
+        }
+        V->arena = nullptr;
+        V->jobs = nullptr;
         pt.lap("overlap");
       }
     });
@@ -759,6 +776,7 @@ class StaticKeySet final : public KeySet {
   std::string DeviceStatus() override { return eng_.status(); }
   int DeviceRecoveries() override { return eng_.recoveries(); }
   int DebugFailVerify(int n) override { return eng_.debug_fail_verify(n); }
+  Engine& engine() override { return eng_; }
   // The key list never changes: no lock; concurrent calls pipeline on the device.
   std::shared_ptr<Verified> verify_raw(const std::vector<std::string_view>& tokens,
                                        const Overlap* overlap = nullptr) override {
@@ -843,6 +861,7 @@ class JSONWebKeySet final : public KeySet {
   std::string DeviceStatus() override { return eng_.status(); }
   int DeviceRecoveries() override { return eng_.recoveries(); }
   int DebugFailVerify(int n) override { return eng_.debug_fail_verify(n); }
+  Engine& engine() override { return eng_; }
   std::shared_ptr<Verified> verify_raw(const std::vector<std::string_view>& tokens,
                                        const Overlap* overlap = nullptr) override {
     auto V = std::make_shared<Verified>();
@@ -1665,6 +1684,39 @@ ClaimField claim_field(const std::string& key) {
 }
 }  // namespace
 
+Leeways resolve_leeways(const Expected& expected) {
+  Leeways l;
+  auto seconds = [](int64_t d) {
+    double lw = dur_seconds(d);
+    if (lw < 0) lw = 0;
+    else if (lw == 0) lw = DefaultLeewaySeconds;
+    return go_f64_to_i64(lw);
+  };
+  l.exp_s = seconds(expected.ExpirationLeeway);
+  l.nbf_s = seconds(expected.NotBeforeLeeway);
+  l.skew_ns = expected.ClockSkewLeeway;
+  if (dur_seconds(l.skew_ns) < 0) l.skew_ns = 0;
+  else if (dur_seconds(l.skew_ns) == 0) l.skew_ns = 60 * kSecond;   // jwt.DefaultLeeway = 1 minute
+  return l;
+}
+
+namespace {
+// validateSigningAlgorithm (jwt/jwt.go:207-239)  [R36]: "" or Validate's error
+std::string alg_header_error(const TokenView& info, const Expected& expected) {
+  std::string e = SupportedSigningAlgorithm(expected.SigningAlgorithms);
+  if (e.empty() && !info.parsed) e = std::string(info.parse_err);
+  if (e.empty() && (info.nsigs == 0 || (info.nsigs == 1 && info.sig0_len == 0))) e = "token must be signed";
+  if (e.empty() && info.nsigs > 1) e = "token with multiple signatures not supported";
+  if (e.empty()) {
+    bool found = false;
+    if (expected.SigningAlgorithms.empty()) found = info.alg == "RS256";
+    for (const auto& a : expected.SigningAlgorithms) found = found || a == info.alg;
+    if (!found) e = "token signed with unexpected algorithm";
+  }
+  return e.empty() ? e : "invalid algorithm (alg) header parameter: " + e;
+}
+}  // namespace
+
 Result validate_claims(const json::Value& all_claims, const TokenInfo& info, const Expected& expected,
                        int64_t now_unix_ns) {
   return validate_claims(all_claims, TokenView{info.parsed, info.parse_err, info.nsigs, info.sig0_len, info.alg},
@@ -1674,23 +1726,8 @@ Result validate_claims(const json::Value& all_claims, const TokenInfo& info, con
 Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
                        int64_t now_unix_ns) {
   Result r;
-  // validateSigningAlgorithm (jwt/jwt.go:207-239)  [R36]
-  {
-    std::string e = SupportedSigningAlgorithm(expected.SigningAlgorithms);
-    if (e.empty() && !info.parsed) e = std::string(info.parse_err);
-    if (e.empty() && (info.nsigs == 0 || (info.nsigs == 1 && info.sig0_len == 0))) e = "token must be signed";
-    if (e.empty() && info.nsigs > 1) e = "token with multiple signatures not supported";
-    if (e.empty()) {
-      bool found = false;
-      if (expected.SigningAlgorithms.empty()) found = info.alg == "RS256";
-      for (const auto& a : expected.SigningAlgorithms) found = found || a == info.alg;
-      if (!found) e = "token signed with unexpected algorithm";
-    }
-    if (!e.empty()) {
-      r.err = "invalid algorithm (alg) header parameter: " + e;
-      return r;
-    }
-  }
+  r.err = alg_header_error(info, expected);
+  if (!r.err.empty()) return r;
   // json.Marshal(allClaims) -> json.Unmarshal(&jwt.Claims{})  [R37]: members in
   // sorted key order, each assigned to the case-insensitively matching field.
   // The fields are views into all_claims (which outlives this call).
@@ -1755,26 +1792,16 @@ Result validate_claims(const json::Value& all_claims, const TokenView& info, con
     r.err = "no issued at (iat), not before (nbf), or expiration time (exp) claims in token";
     return r;
   }
+  const Leeways lw = resolve_leeways(expected);
   if (exp == 0) {
     const int64_t latest = nbf > iat ? nbf : iat;
-    double lw = dur_seconds(expected.ExpirationLeeway);
-    if (lw < 0) lw = 0;
-    else if (lw == 0) lw = DefaultLeewaySeconds;
-    exp = (int64_t)((uint64_t)latest + (uint64_t)go_f64_to_i64(lw));
+    exp = (int64_t)((uint64_t)latest + (uint64_t)lw.exp_s);
   }
   if (nbf == 0) {
-    if (iat != 0) {
-      nbf = iat;
-    } else {
-      double lw = dur_seconds(expected.NotBeforeLeeway);
-      if (lw < 0) lw = 0;
-      else if (lw == 0) lw = DefaultLeewaySeconds;
-      nbf = (int64_t)((uint64_t)exp - (uint64_t)go_f64_to_i64(lw));
-    }
+    if (iat != 0) nbf = iat;
+    else nbf = (int64_t)((uint64_t)exp - (uint64_t)lw.nbf_s);
   }
-  int64_t cks = expected.ClockSkewLeeway;
-  if (dur_seconds(cks) < 0) cks = 0;
-  else if (dur_seconds(cks) == 0) cks = 60 * kSecond;           // jwt.DefaultLeeway = 1 minute
+  const int64_t cks = lw.skew_ns;
   // registered claims (jwt/jwt.go:172-184)  [R39]
   if (!expected.Issuer.empty() && expected.Issuer != iss) { r.err = "invalid issuer (iss) claim"; return r; }
   if (!expected.Subject.empty() && expected.Subject != sub) { r.err = "invalid subject (sub) claim"; return r; }
@@ -1836,6 +1863,178 @@ Results Validator::ValidateBatch(const std::vector<std::string_view>& tokens, co
   return ks_->verify_batch(tokens, &post);
 }
 
+namespace {
+// the string Validate gives for a jg_claim_code (jwt/jwt.go:117-199)
+const char* claim_code_error(uint8_t code) {
+  switch (code) {
+    case JG_CL_NO_TIME: return "no issued at (iat), not before (nbf), or expiration time (exp) claims in token";
+    case JG_CL_ISS: return "invalid issuer (iss) claim";
+    case JG_CL_SUB: return "invalid subject (sub) claim";
+    case JG_CL_JTI: return "invalid ID (jti) claim";
+    case JG_CL_AUD: return "invalid audience (aud) claim: audience claim does not match any expected audience";
+    case JG_CL_NBF: return "invalid not before (nbf) claim: token not yet valid";
+    case JG_CL_EXP: return "invalid expiration time (exp) claim: token is expired";
+    case JG_CL_IAT: return "invalid issued at (iat) claim: token issued in the future";
+    default: return "";
+  }
+}
+}  // namespace
+
+namespace {
+// CheckBatch's flow; put(i, ok, err) receives token i's outcome once, from a
+// host thread (CheckBatch keeps the strings, CheckVerdicts only the bit)
+template <class Put>
+void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected& expected, CheckStats* stats,
+                Put&& put) {
+  const int64_t now = expected.has_now ? expected.now_unix_ns : wall_now_ns();
+  const size_t n = tokens.size();
+  const int th = host_threads();
+  // the resolved Expected of the scan (include/jg.h jg_expect); one the ABI
+  // does not take (more than JG_MAX_AUD audiences, strings over
+  // JG_EXPECT_MAX_BYTES) leaves every token to the host path
+  jg_expect ex{};
+  std::string strs = expected.Issuer + expected.Subject + expected.ID;
+  ex.iss_len = (uint32_t)expected.Issuer.size();
+  ex.sub_len = (uint32_t)expected.Subject.size();
+  ex.jti_len = (uint32_t)expected.ID.size();
+  bool scannable = expected.Audiences.size() <= JG_MAX_AUD;
+  if (scannable) {
+    ex.naud = (uint32_t)expected.Audiences.size();
+    for (size_t k = 0; k < expected.Audiences.size(); ++k) {
+      ex.aud_len[k] = (uint32_t)expected.Audiences[k].size();
+      strs += expected.Audiences[k];
+    }
+  }
+  scannable = scannable && strs.size() <= JG_EXPECT_MAX_BYTES;
+  ex.strs = (const uint8_t*)strs.data();
+  {
+    int64_t s = now / kSecond, ns = now % kSecond;
+    if (ns < 0) { ns += kSecond; --s; }
+    ex.now_sec = s;
+    ex.now_nsec = (uint32_t)ns;
+  }
+  const Leeways lw = resolve_leeways(expected);
+  ex.skew_ns = lw.skew_ns;
+  ex.exp_leeway_s = lw.exp_s;
+  ex.nbf_leeway_s = lw.nbf_s;
+  // code[i]: the device's verdict on token i's registered claims; JG_CL_HOST
+  // also for a token that was never scanned.  Job i is token i's payload
+  // segment inside the arena the signatures are verified from (a canonical
+  // compact token is copied there as it is); len 0 = not in the arena.
+  // Both arrays live in one pinned block of the engine's pool (DMA at link
+  // speed, no page faults in steady state).
+  Engine& eng = ks_->engine();
+  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + 16);
+  jg_cjob* const jobs = (jg_cjob*)scanbuf.get();
+  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob);
+  std::memset(code, JG_CL_HOST, n);
+  bool have_jobs = false;
+  bool scan_failed = false;
+  std::string scan_err;
+  uint64_t scan_seen = 0;
+  const KeySet::Overlap overlap = [&](const Verified& V) {
+    if (!scannable || !V.arena || n == 0) return;
+    PhaseTimer pt("check");
+    have_jobs = true;
+    parallel_for(n, th, [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i) {
+        const Tok& t = V.toks[i];
+        jg_cjob& j = jobs[i];
+        j.off = 0;
+        j.len = 0;
+        j.flags = 0;
+        if (!t.ncand || !t.lit) continue;
+        const char* dot = (const char*)std::memchr(t.lit, '.', t.si_len);
+        if (!dot) continue;
+        const size_t d1 = (size_t)(dot - t.lit);
+        j.off = V.jobs[t.job0].off + d1 + 1;
+        j.len = (uint32_t)(t.si_len - d1 - 1);
+      }
+    });
+    pt.lap("scan-jobs");
+    try {
+      eng.claims_scan(V.arena, V.arena_len, jobs, n, &ex, code, true);
+    } catch (const DeviceError& e) {
+      // as a failed verify: the tokens the scan carried get its error (no
+      // host fallback for them) and the context is recreated after the batch
+      scan_failed = true;
+      scan_err = std::string("capjwt: claims scan unavailable: ") + e.what();
+      scan_seen = eng.errors();
+    }
+    pt.lap("scan");
+  };
+  std::shared_ptr<Verified> V = ks_->verify_raw(tokens, &overlap);
+  if (scan_failed) (void)eng.recover(scan_seen);
+  PhaseTimer pt("check");
+  const Chunks ch = make_chunks(n, th);
+  std::vector<size_t> n_scan(ch.count(), 0), n_host(ch.count(), 0);
+  run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
+    size_t ns = 0, nh = 0;
+    for (size_t i = lo; i < hi; ++i) {
+      const Tok& t = V->toks[i];
+      if (!(t.parsed && !V->failed[i] && V->any[i])) {
+        Result r;                                     // the key set's own error string; no claims are read
+        ks_->finish(*V, i, r);
+        put(i, false, "error verifying token signature: " + r.err);
+        continue;
+      }
+      if (scan_failed && have_jobs && jobs[i].len) {
+        put(i, false, std::string(scan_err));
+        continue;
+      }
+      if (code[i] == JG_CL_HOST) {
+        ++nh;
+        Result r;
+        ks_->finish(*V, i, r);
+        if (!r.ok) {
+          put(i, false, "error verifying token signature: " + r.err);
+          continue;
+        }
+        Result v = validate_claims(r.claims, t.view(), expected, now);
+        put(i, v.ok, std::move(v.err));
+        continue;
+      }
+      ++ns;
+      std::string err = alg_header_error(t.view(), expected);
+      if (!err.empty()) {
+        put(i, false, std::move(err));
+        continue;
+      }
+      put(i, code[i] == JG_CL_OK, std::string(claim_code_error(code[i])));
+    }
+    n_scan[c] = ns;
+    n_host[c] = nh;
+  });
+  pt.lap("merge");
+  if (stats) {
+    stats->scanned = stats->host = 0;
+    for (size_t c = 0; c < ch.count(); ++c) {
+      stats->scanned += n_scan[c];
+      stats->host += n_host[c];
+    }
+  }
+  V->toks.release();
+  pt.lap("free-toks");
+}
+}  // namespace
+
+std::vector<CheckResult> Validator::CheckBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                               CheckStats* stats) {
+  std::vector<CheckResult> out(tokens.size());
+  check_core(ks_, tokens, expected, stats, [&](size_t i, bool ok, std::string&& err) {
+    out[i].ok = ok;
+    out[i].err = std::move(err);
+  });
+  return out;
+}
+
+std::vector<uint8_t> Validator::CheckVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                              CheckStats* stats) {
+  std::vector<uint8_t> ok(tokens.size(), 0);
+  check_core(ks_, tokens, expected, stats, [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
+  return ok;
+}
+
 // ====================================================================== oidc hash claims
 void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, uint8_t* digests) {
   std::shared_lock<std::shared_mutex> life(life_);
@@ -1843,6 +2042,25 @@ void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size
   const int rc = jg_hash_batch(ctx_, arena, arena_len, (const jg_hjob*)jobs, njobs, digests);
   if (rc == -1) throw std::logic_error(std::string("capjwt: jg_hash_batch rejected the host's jobs: ") + jg_last_error(ctx_));
   if (rc != 0) fail_device(std::string("capjwt: jg_hash_batch: ") + jg_last_error(ctx_));
+}
+
+// jg_claims_scan is the one ABI entry the host layer binds weakly: an ABI
+// provider without it (the stub ABI the CPU unit tests link, an older
+// libcapjwt.so) still links, and a CheckBatch against it reports the scan as
+// unavailable, as any other device failure.
+extern "C" __attribute__((weak)) int jg_claims_scan(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
+                                                    const jg_expect*, uint8_t*);
+
+void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
+                         uint8_t* codes, bool inside_verify) {
+  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
+  if (!inside_verify) life.lock();
+  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
+  if (!jg_claims_scan) fail_device("capjwt: jg_claims_scan: not provided by the loaded verifier library");
+  const int rc = jg_claims_scan(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect, codes);
+  if (rc == -1)
+    throw std::logic_error(std::string("capjwt: jg_claims_scan rejected the host's jobs: ") + jg_last_error(ctx_));
+  if (rc != 0) fail_device(std::string("capjwt: jg_claims_scan: ") + jg_last_error(ctx_));
 }
 
 namespace {

@@ -15,6 +15,7 @@
 //   ParsePublicKeyPEM         jwt/keyset.go:178-200   ParsePublicKeyPEM
 //   NewValidator / Validate   jwt/jwt.go:25-202       NewValidator / Validator::Validate
 //   (north star) ValidateBatch                        Validator::ValidateBatch
+//   (verdict only) CheckBatch                         Validator::CheckBatch (claims scanned on the GPU)
 //   SupportedSigningAlgorithm jwt/algs.go:38-46       SupportedSigningAlgorithm
 //
 // There is no CPU verification path: a KeySet whose GPU context cannot be
@@ -186,6 +187,12 @@ class Engine {
               const std::function<void()>& submitted = {});
   // SHA-2 of (arena span, family) jobs: digests njobs x 64 bytes (jg_hash_batch)
   void hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, uint8_t* digests);
+  // registered-claims scan of (arena span) jobs against one resolved Expected
+  // (jg_cjob / jg_expect): codes[i] = a jg_claim_code (jg_claims_scan).
+  // inside_verify: called from verify()'s `submitted` callback, on its thread
+  // (that call already holds the context's lifetime lock).
+  void claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
+                   uint8_t* codes, bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -348,6 +355,7 @@ class KeySet {
   virtual std::string DeviceStatus() = 0;
   virtual int DeviceRecoveries() = 0;
   virtual int DebugFailVerify(int n) = 0;            // jg_debug_fail_verify on its context (tests)
+  virtual Engine& engine() = 0;                      // the device context (Validator::CheckBatch's claims scan)
  private:
   Coalescer co_;
 };
@@ -401,11 +409,37 @@ struct Expected {                                      // jwt/jwt.go:38-83
   int64_t now_unix_ns = 0;
 };
 
+// Validate's (ok, error string) for one token, without the claims map
+struct CheckResult {
+  bool ok = false;
+  std::string err;
+};
+// Where a CheckBatch call's claim verdicts came from: tokens whose registered
+// claims the device decided / tokens that took the host path (claims map +
+// validate_claims).  Tokens that fail before the claims (parse, signature) are
+// in neither.
+struct CheckStats {
+  size_t scanned = 0, host = 0;
+};
+
 class Validator {
  public:
   explicit Validator(KeySet* ks) : ks_(ks) {}
   Result Validate(std::string_view token, const Expected& expected);
   Results ValidateBatch(const std::vector<std::string_view>& tokens, const Expected& expected);
+  // Verdict-only ValidateBatch: out[i] is Validate(tokens[i], expected)'s (ok,
+  // error string), token for token, and no claims map is built for a token
+  // whose registered claims the device decides.  Parse and signatures as
+  // ValidateBatch; the payload segments are scanned on the GPU
+  // (jg_claims_scan) while the signature batch is on the device; the alg
+  // header check stays on the host.  A token the scan leaves to the host
+  // (JG_CL_HOST, b64:false, a re-encoded token) takes today's path alone.
+  std::vector<CheckResult> CheckBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                      CheckStats* stats = nullptr);
+  // CheckBatch's accept bits alone (1 = Validate returns no error): no error
+  // string outlives the call (CheckBlob)
+  std::vector<uint8_t> CheckVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                     CheckStats* stats = nullptr);
  private:
   KeySet* ks_;
 };
@@ -418,6 +452,15 @@ Result validate_claims(const json::Value& all_claims, const TokenInfo& info, con
                        int64_t now_unix_ns);
 Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
                        int64_t now_unix_ns);
+// Expected's three leeways after Go's defaulting (jwt/jwt.go:128-170): the
+// clock skew in ns (negative -> 0, 0 -> one minute) and the leeways that
+// default a missing exp / nbf, as the whole seconds Go adds (negative -> 0,
+// 0 -> 150 s, then int64(float64 seconds)).  validate_claims and the claims
+// scan's resolved Expected share it.
+struct Leeways {
+  int64_t skew_ns = 0, exp_s = 0, nbf_s = 0;
+};
+Leeways resolve_leeways(const Expected& expected);
 
 bool ParsePublicKeyPEM(std::string_view data, PublicKey* out, std::string* err);
 

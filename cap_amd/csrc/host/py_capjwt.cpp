@@ -436,6 +436,51 @@ PYBIND11_MODULE(_capjwt_host, m) {
         }
         return py::bytes(ok);
       })
+      .def("check_batch", [](PyValidator& s, py::sequence toks, const Expected& e) {
+        // verdict only: (list of error strings or None, tokens the device's
+        // claims scan decided, tokens that took the host claims path)
+        auto v = as_strings(toks);
+        std::vector<CheckResult> rs;
+        CheckStats st;
+        {
+          py::gil_scoped_release rel;
+          rs = s.v->CheckBatch(views(v), e, &st);
+        }
+        py::list out(rs.size());
+        for (size_t i = 0; i < rs.size(); ++i) {
+          if (rs[i].ok) out[i] = py::none();
+          else out[i] = py::str(rs[i].err);
+        }
+        return py::make_tuple(out, st.scanned, st.host);
+      })
+      .def("check_blob", [](PyValidator& s, py::bytes blob, const Expected& e) {
+        // validate_blob's verdict-only twin: newline-separated tokens in,
+        // (accept bytes, scanned, host) out
+        char* bp = nullptr;
+        Py_ssize_t bn = 0;
+        if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+        std::string ok;
+        CheckStats st;
+        {
+          py::gil_scoped_release rel;
+          const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+          auto t0 = std::chrono::steady_clock::now();
+          auto lap = [&](const char* what) {
+            if (!trace) return;
+            const auto t1 = std::chrono::steady_clock::now();
+            std::fprintf(stderr, "[capjwt] cblob %-12s %8.2f ms\n", what,
+                         std::chrono::duration<double, std::milli>(t1 - t0).count());
+            t0 = t1;
+          };
+          auto toks = split_lines(bp, (size_t)bn);
+          lap("split");
+          const auto rs = s.v->CheckVerdicts(toks, e, &st);
+          lap("check");
+          ok.assign((const char*)rs.data(), rs.size());
+          lap("verdicts");
+        }
+        return py::make_tuple(py::bytes(ok), st.scanned, st.host);
+      })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {
         // Measurement helper (bench.py `single`): `callers` host threads, each

@@ -49,6 +49,7 @@
 #include "kernels/common.hpp"
 #include "kernels/ecdsa.hpp"
 #include "kernels/ed25519.hpp"
+#include "kernels/claims.hpp"
 #include "kernels/hash.hpp"
 #include "kernels/prep.hpp"
 #include "host_mont.hpp"
@@ -678,6 +679,11 @@ struct Device {
   Lane lane1;                     // resident batches staged second, fourth, ...
   hipStream_t kstream = nullptr;  // key loads (staging, narrow tables): beside the verify streams
   hipStream_t ustream = nullptr;  // background width upgrades of key comb tables
+  // jg_claims_scan: a stream and buffers of its own (kept between calls), one
+  // scan at a time; nothing of lane0 / the slots, so d->mu is not taken
+  hipStream_t clstream = nullptr;
+  std::mutex cl_mu;
+  Grow cl_arena, cl_jobs, cl_out, cl_expect;
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -2870,6 +2876,7 @@ jg_ctx* jg_create(const int* devices, int ndev) {
       }
       HIPCHK(hipStreamCreateWithFlags(&d->kstream, hipStreamNonBlocking));
       HIPCHK(hipStreamCreateWithFlags(&d->ustream, hipStreamNonBlocking));
+      HIPCHK(hipStreamCreateWithFlags(&d->clstream, hipStreamNonBlocking));
       ctx->devs.push_back(std::move(d));
     }
     auto ks = std::make_shared<KeyState>();        // no keys yet: every job is out of range
@@ -2932,7 +2939,7 @@ void jg_destroy(jg_ctx* ctx) {
       (void)hipStreamSynchronize(d->copy);
       (void)hipStreamDestroy(d->copy);
     }
-    for (hipStream_t* st : {&d->kstream, &d->ustream})
+    for (hipStream_t* st : {&d->kstream, &d->ustream, &d->clstream})
       if (*st) {
         (void)hipStreamSynchronize(*st);
         (void)hipStreamDestroy(*st);
@@ -3346,6 +3353,50 @@ int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
       digest_out[4 * k + 2] = (uint8_t)(w[k] >> 8);
       digest_out[4 * k + 3] = (uint8_t)w[k];
     }
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(e.what());
+    return -2;
+  }
+}
+
+int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                   const jg_cjob* jobs, size_t njobs, const jg_expect* expect, uint8_t* code_out) {
+  if (!ctx || !expect || (njobs > 0 && (!jobs || !code_out)) || (arena_len > 0 && !arena)) return -1;
+  if (njobs == 0) return 0;
+  if (ctx->poisoned.load()) {
+    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
+    return -2;
+  }
+  auto E = std::make_unique<jgclaims::Expect>();
+  if (!jgclaims::resolve(*expect, E.get())) {
+    ctx->set_err("jg_claims_scan: more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9");
+    return -1;
+  }
+  for (size_t i = 0; i < njobs; ++i) {
+    const jg_cjob& J = jobs[i];
+    if (J.flags != 0 || J.off > arena_len || J.len > arena_len - J.off) {
+      ctx->set_err("jg_claims_scan: job " + std::to_string(i) + " has flags set or a span past the arena");
+      return -1;
+    }
+  }
+  try {
+    Device* d = ctx->devs[0].get();
+    std::lock_guard<std::mutex> g(d->cl_mu);
+    HIPCHK(hipSetDevice(d->id));
+    const hipStream_t s = d->clstream;
+    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
+    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
+    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
+    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
+    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
+    jgclaims::Expect* e = (jgclaims::Expect*)d->cl_expect.get(sizeof(jgclaims::Expect));
+    HIPCHK(hipMemcpyAsync(e, E.get(), sizeof(jgclaims::Expect), hipMemcpyHostToDevice, s));
+    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
+    launch_claims_scan(a, j, (int64_t)njobs, e, o, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return 0;
   } catch (const std::exception& e) {
     ctx->set_err(e.what());

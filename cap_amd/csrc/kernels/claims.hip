@@ -1,0 +1,64 @@
+// claims.hip -- batched scan of the registered claims on gfx950.
+//
+// The claim checks of cap's Validator.Validate after the signature
+// (jwt/jwt.go:103-201) for callers that need the verdict only: one lane per
+// token decodes the base64url payload segment and walks the JSON text with the
+// scalar state machine of claims.hpp (claims_decide), reading the arena through
+// aligned 32-bit words as hash.hip's MemString does -- one word load per four
+// characters, never more than seven bytes past the segment (ARENA_SLACK covers
+// it).  The resolved Expected (window edges, leeways, expected strings) is
+// copied to LDS once per block; the byte compares of a claim value against the
+// expected strings are LDS reads.  A wave runs until its longest payload ends.
+#include <hip/hip_runtime.h>
+
+#include "claims.hpp"
+
+using namespace jgclaims;
+
+namespace {
+
+// characters [4g, 4g+4) of a segment that starts `shift` bytes into aligned[0]
+struct WordSrc {
+  const uint32_t* aligned;
+  uint32_t shift8;            // 8 * (offset & 3)
+  uint32_t cur;               // aligned[g]
+  __device__ __forceinline__ uint32_t word(uint32_t g) {
+    const uint32_t nxt = aligned[g + 1];
+    const uint32_t w = (uint32_t)((((uint64_t)nxt << 32) | cur) >> shift8);
+    cur = nxt;
+    return w;
+  }
+};
+
+constexpr int kBlock = 256;
+
+__global__ void __launch_bounds__(kBlock) k_claims_scan(const uint8_t* __restrict__ arena,
+                                                        const jg_cjob* __restrict__ jobs, int64_t n,
+                                                        const Expect* __restrict__ expect,
+                                                        uint8_t* __restrict__ code_out) {
+  __shared__ Expect E;
+  {
+    static_assert(sizeof(Expect) % 4 == 0, "Expect is copied by words");
+    const uint32_t* src = (const uint32_t*)expect;
+    uint32_t* dst = (uint32_t*)&E;
+    for (uint32_t k = threadIdx.x; k < sizeof(Expect) / 4; k += kBlock) dst[k] = src[k];
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const jg_cjob J = jobs[i];
+  WordSrc src;
+  src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
+  src.shift8 = 8u * (uint32_t)(J.off & 3);
+  src.cur = src.aligned[0];
+  code_out[i] = claims_decide(src, J.len, E);
+}
+
+}  // namespace
+
+void launch_claims_scan(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
+                        uint8_t* code_out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_claims_scan, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs, n,
+                     expect, code_out);
+}

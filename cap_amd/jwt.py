@@ -13,6 +13,8 @@ returns become `(value, err)` tuples with `err` a str or None.
     jwt.ParsePublicKeyPEM    jwt/keyset.go:178       ParsePublicKeyPEM
     jwt.NewValidator         jwt/jwt.go:25           NewValidator
     Validator.Validate       jwt/jwt.go:95           Validator.Validate (+ ValidateBatch, north star)
+    (verdict only)                                   Validator.CheckBatch / CheckBlob: Validate's error per
+                                                     token, registered claims scanned on the GPU, no claims map
     jwt.Expected             jwt/jwt.go:38           Expected
     jwt.SupportedSigningAlgorithm jwt/algs.go:38     SupportedSigningAlgorithm
 
@@ -170,6 +172,24 @@ class Validator:
     def ValidateBlob(self, blob: bytes, expected: Expected = None) -> bytes:
         """Newline-separated tokens -> one accept byte per token (throughput entry)."""
         return self._impl.validate_blob(blob, (expected or Expected())._native())
+
+    def CheckBatch(self, tokens: Sequence, expected: Expected = None, stats: dict = None):
+        """Verdict-only ValidateBatch: [err or None], err == Validate(tokens[i], expected)[1].
+        The registered claims are scanned on the GPU and no claims map is built
+        for a token the scan decides.  `stats` (a dict) receives {"scanned": tokens
+        the device decided, "host": tokens that took the host claims path}."""
+        errs, scanned, host = self._impl.check_batch(list(tokens), (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return errs
+
+    def CheckBlob(self, blob: bytes, expected: Expected = None, stats: dict = None) -> bytes:
+        """ValidateBlob's verdict-only twin (CheckBatch): newline-separated tokens ->
+        one accept byte per token; `stats` as in CheckBatch."""
+        ok, scanned, host = self._impl.check_blob(blob, (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return ok
 
 
 def NewValidator(keyset: Optional[KeySet]):

@@ -283,6 +283,72 @@ typedef struct jg_hjob {
 int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                   const jg_hjob* jobs, size_t njobs, uint8_t* digest_out);
 
+/* ---- batched scan of the registered claims ----
+ * The claim checks of cap's Validator.Validate after the signature and the alg
+ * header (jwt/jwt.go:103-201: iss / sub / jti / aud and the nbf / exp / iat
+ * window), decided on the device for callers that need the verdict and not the
+ * claims map.  Job i names the base64url payload segment of one token: the
+ * bytes between its two dots, unpadded, at arena[off, off + len); flags is
+ * reserved, 0.  `expect` is one resolved jwt.Expected for the whole call:
+ *  - strs: issuer, subject, id and the audiences back to back (lengths in
+ *    iss_len, sub_len, jti_len, aud_len[0..naud)); an empty string is "not
+ *    expected"; at most JG_MAX_AUD audiences and JG_EXPECT_MAX_BYTES in all;
+ *  - now as unix (seconds, nanoseconds in [0, 1e9));
+ *  - skew_ns: the clock-skew leeway after Go's defaulting (negative -> 0,
+ *    0 -> one minute);
+ *  - exp_leeway_s / nbf_leeway_s: the leeways that default a missing exp / nbf,
+ *    in whole seconds, after defaulting (negative -> 0, 0 -> 150 s) and
+ *    Go's int64(float64) conversion.
+ * code_out[i] receives a jg_claim_code: the first failing check in Validate's
+ * order (no-time, iss, sub, jti, aud, nbf, exp, iat), JG_CL_OK, or JG_CL_HOST.
+ * The scan is conservative: any code other than JG_CL_HOST is exactly what the
+ * host's claim checks return for that payload; JG_CL_HOST means the device
+ * does not decide and the caller must (a payload that is not canonical
+ * base64url of one well-formed JSON object, an escape or a control byte in a
+ * string, a registered claim named twice or of an unexpected type, a date that
+ * is not a plain integer of at most 15 digits, ... -- DESIGN.md lists the
+ * rules).
+ * Blocking; runs on the context's first device on a stream of its own, so it
+ * may be called while a jg_submit of another thread is in flight and does not
+ * queue behind it; concurrent scans of one context run one after the other.
+ * Device buffers are kept between calls.  Returns 0; -1 on bad arguments (a
+ * span past arena_len, nonzero flags, more than JG_MAX_AUD audiences, expected
+ * strings over JG_EXPECT_MAX_BYTES, now_nsec out of range); -2 on an
+ * infrastructure error and in a context a device failure has made unusable.
+ * njobs == 0 returns 0 without touching the buffers. */
+#define JG_MAX_AUD 16
+#define JG_EXPECT_MAX_BYTES 4096
+enum jg_claim_code {
+  JG_CL_OK = 0,      /* every check passed */
+  JG_CL_NO_TIME = 1, /* "no issued at (iat), not before (nbf), or expiration time (exp) claims in token" */
+  JG_CL_ISS = 2,     /* "invalid issuer (iss) claim" */
+  JG_CL_SUB = 3,     /* "invalid subject (sub) claim" */
+  JG_CL_JTI = 4,     /* "invalid ID (jti) claim" */
+  JG_CL_AUD = 5,     /* "invalid audience (aud) claim: audience claim does not match any expected audience" */
+  JG_CL_NBF = 6,     /* "invalid not before (nbf) claim: token not yet valid" */
+  JG_CL_EXP = 7,     /* "invalid expiration time (exp) claim: token is expired" */
+  JG_CL_IAT = 8,     /* "invalid issued at (iat) claim: token issued in the future" */
+  JG_CL_HOST = 9     /* the device does not decide; the host must */
+};
+typedef struct jg_cjob {
+  uint64_t off;
+  uint32_t len;
+  uint32_t flags;          /* reserved, 0 */
+} jg_cjob;
+typedef struct jg_expect {
+  const uint8_t* strs;
+  uint32_t iss_len, sub_len, jti_len;
+  uint32_t naud;
+  uint32_t aud_len[JG_MAX_AUD];
+  int64_t now_sec;
+  uint32_t now_nsec;
+  uint32_t pad_;
+  int64_t skew_ns;
+  int64_t exp_leeway_s, nbf_leeway_s;
+} jg_expect;
+int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                   const jg_cjob* jobs, size_t njobs, const jg_expect* expect, uint8_t* code_out);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 
