@@ -143,6 +143,36 @@ uint64_t default_table_budget() {
   return b;
 }
 
+// Debugging knobs of the persistent k_ec_point (kernels/ecdsa_impl.hpp):
+//   CAPJWT_DEBUG_EC_POINT=1         EC launches of every size run k_ec_point
+//                                   (not the split / prefetch kernels of small launches)
+//   CAPJWT_DEBUG_EC_POINT_BLOCKS=n  the persistent kernel's grid is n blocks, whatever
+//                                   JG_EC_POINT_SLOTS, the device and the launch's
+//                                   size give (n >= 1; blocks past the groups exit)
+bool ec_force_point() {
+  static const bool on = [] {
+    const char* e = std::getenv("CAPJWT_DEBUG_EC_POINT");
+    return e && std::atoi(e) != 0;
+  }();
+  return on;
+}
+int ec_point_blocks_env() {
+  static const int n = [] {
+    const char* e = std::getenv("CAPJWT_DEBUG_EC_POINT_BLOCKS");
+    const long v = e ? std::atol(e) : 0;
+    return v >= 1 && v <= (1 << 24) ? (int)v : 0;
+  }();
+  return n;
+}
+// k_ec_point's grid cap in blocks for a class on a device of `simds` SIMDs
+// (0: no cap): JG_EC_POINT_SLOTS waves per SIMD for the curves whose kernel
+// loops (ec_point_persistent), none for the others
+int ec_point_blocks(int simds, int cls) {
+  if (!ec_point_persistent(cls)) return 0;
+  if (const int n = ec_point_blocks_env()) return n;
+  return JG_EC_POINT_SLOTS * simds;
+}
+
 // Chunk boundaries of jobs [lo, hi) for a pipeline of C-job chunks: the first
 // chunks ramp up from 4096 jobs (the copy engine starts after a short host
 // plan) and the tail ends in a quarter-size chunk (little kernel time left
@@ -675,6 +705,7 @@ class Helper {
 
 struct Device {
   int id = 0;
+  int simds = 0;                  // compute units x 4 (jg_create)
   Lane lane0;                     // resident batches, hashing
   Lane lane1;                     // resident batches staged second, fourth, ...
   hipStream_t kstream = nullptr;  // key loads (staging, narrow tables): beside the verify streams
@@ -1092,7 +1123,7 @@ void size_scratch(Bufs* B, const Plan& P, size_t arena_bytes) {
   B->rows.get(sizeof(uint32_t) * (size_t)P.scratch_rows * npad);
   B->pss.get((size_t)std::max<int64_t>(P.pss_tokens, 1) * 2048);
   B->exc.get(sizeof(int32_t) * npad);
-  B->exc_cnt.get(sizeof(uint32_t) * NCLS);
+  B->exc_cnt.get(sizeof(uint32_t) * NCLS * 2);   // exception counts, then k_ec_point's group counters
 }
 
 // resident batch: arena (slack zeroed), jobs and perm placed by the host
@@ -1371,6 +1402,10 @@ void run_plan(Device* d, const KeyState& K, const DevGen& G, Lane* L, Bufs* B, c
       ea.gtab = d->gtab[c];
       ea.exc_list = (int32_t*)B->exc.p + r.begin;
       ea.exc_count = (uint32_t*)B->exc_cnt.p + c;
+      ea.grp_next = (uint32_t*)B->exc_cnt.p + NCLS + c;
+      ea.point_blocks = ec_point_blocks(d->simds, c);
+      ea.force_point = ec_force_point();
+      ea.point_exact = ec_point_persistent(c) && ec_point_blocks_env() != 0;
       ea.npad = np;
       ea.exc_reset = 1;
       // class-grouped chunks: the exact kernels wait for the join lane (below).
@@ -2855,6 +2890,9 @@ jg_ctx* jg_create(const int* devices, int ndev) {
       auto d = std::make_unique<Device>();
       d->id = id;
       HIPCHK(hipSetDevice(id));
+      int cus = 0;
+      HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, id));
+      d->simds = cus * 4;          // four SIMDs per compute unit (GCN / CDNA)
       HIPCHK(hipStreamCreateWithFlags(&d->copy, hipStreamNonBlocking));
       for (auto& l : d->lanes) l.create_main();
       d->lane0.create_main();

@@ -27,8 +27,27 @@ struct EcArgs {
   // which kernels launch_ec enqueues: EC_ALL (scalar, point, exact), EC_FAST
   // (scalar, point) or EC_EXACT (exact alone, later, on another stream)
   int32_t part;
+  // k_ec_point is persistent: its waves take 64-token groups of [begin, end)
+  // from *grp_next until none is left.  The scalar launch before it on the
+  // stream zeroes the counter (as exc_reset does the exception counter).
+  uint32_t* grp_next;
+  int32_t point_blocks;       // k_ec_point's grid, at most this many one-wave blocks (0: one per group)
+  int32_t force_point;        // debugging: launches of every size run k_ec_point (no split / prefetch path)
+  int32_t point_exact;        // debugging: the grid is point_blocks blocks, also where that is more than the groups
 };
 enum : int32_t { EC_ALL = 0, EC_FAST = 1, EC_EXACT = 2 };
+
+// Waves of k_ec_point per SIMD (the grid is this x the device's SIMDs, or one
+// block per group if that is fewer); 0: one block per 64-token group, as
+// before the kernel looped.  See DESIGN.md section 5 for the A/B.
+#ifndef JG_EC_POINT_SLOTS
+#define JG_EC_POINT_SLOTS 4
+#endif
+// The curves whose k_ec_point loops and takes the cap: P-256.  EdDSA + ES384
+// read 302-310 M/s with the P-384 kernel capped against 305-312 without, so
+// P-384 and P-521 keep one block per group and no counter (grp_next and
+// point_blocks are not read for them).
+constexpr bool ec_point_persistent(int cls) { return cls == jgk::CLS_P256; }
 
 // table geometry per curve: words per entry (x,y Montgomery limbs, 16-B aligned)
 constexpr int ec_limbs(int cls) { return cls == jgk::CLS_P256 ? 10 : cls == jgk::CLS_P384 ? 15 : 20; }

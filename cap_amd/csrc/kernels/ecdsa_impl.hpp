@@ -271,6 +271,9 @@ __global__ void __launch_bounds__(64 * WPB) JG_EC_SCALAR_ATTR k_ec_scalar_batch(
   // to it after this kernel; a separate memset would be one more dependent
   // launch on the lane, waiting for a free wave slot behind the modexps)
   if (a.exc_reset && i == 0) *a.exc_count = 0u;
+  // and every scalar launch rewinds the group counter of the k_ec_point launch
+  // that follows it on the stream
+  if (a.grp_next && i == 0) *a.grp_next = 0u;
   if (WPB == 1 && i >= S) return;                  // (blocks of several waves keep every thread for the barriers)
   uint32_t acc[L];
   mp::set_const<Fn>(acc, Fn::ONE);
@@ -610,14 +613,14 @@ __device__ __forceinline__ void add_raw(uint32_t* X, uint32_t* Y, uint32_t* Z, b
 #ifndef JG_EC_POINT_ATTR
 #define JG_EC_POINT_ATTR
 #endif
+// one token of k_ec_point: the comb sum, the x(R) check, the verdict
 template <class CV>
-__global__ void __launch_bounds__(64) JG_EC_POINT_ATTR k_ec_point(EcArgs a) {
+__device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p) {
   using Fp = typename CV::Fp;
   using Fn = typename CV::Fn;
   constexpr int L = Fp::L;
   constexpr int NG = ec_windows(CV::CLS, true), NQ = ec_windows_w(CV::CLS, CV::WQ);
   constexpr int NWIN = NG > NQ ? NG : NQ;
-  const int64_t p = a.begin + (int64_t)blockIdx.x * WAVE + threadIdx.x;
   const int64_t np = a.npad;
   const JobDev jb = a.jobs[p];
   if (!job_live(jb)) return;
@@ -704,6 +707,33 @@ __global__ void __launch_bounds__(64) JG_EC_POINT_ATTR k_ec_point(EcArgs a) {
     }
   }
   a.verdict_pad[p] = ok;
+}
+
+// Persistent: each one-wave block takes 64-token groups of [begin, end) from
+// *a.grp_next (zeroed by the k_ec_scalar_batch launch before this one) until
+// none is left, so the grid may be any size >= 1 and launch_chain caps it at
+// EcArgs::point_blocks.  A block that starts late, because the other lane's
+// prep or scalar waves held its slot, takes fewer groups; one that finds none
+// exits.  Measured beside it: a block's first group
+// taken from its own index, and no counter at all (block b takes b, b + grid,
+// ...), which was 5-9 % slower per step -- the late blocks then hold the
+// kernel's tail.
+// P-256 only (ec_point_persistent): the P-384 kernel measured no gain under
+// the cap, so P-384 and P-521 keep one block per group.
+template <class CV>
+__global__ void __launch_bounds__(64) JG_EC_POINT_ATTR k_ec_point(EcArgs a) {
+  if constexpr (!ec_point_persistent(CV::CLS)) {
+    ec_point_token<CV>(a, a.begin + (int64_t)blockIdx.x * WAVE + threadIdx.x);
+    return;
+  }
+  const uint32_t groups = (uint32_t)((a.end - a.begin) / WAVE);
+  for (;;) {
+    uint32_t g = 0;
+    if (threadIdx.x == 0) g = atomicAdd(a.grp_next, 1u);
+    g = __builtin_amdgcn_readfirstlane(g);
+    if (g >= groups) return;
+    ec_point_token<CV>(a, a.begin + (int64_t)g * WAVE + threadIdx.x);
+  }
 }
 
 // ------------------------------------------------------------------ exact path
@@ -1236,13 +1266,14 @@ void launch_chain(const EcArgs& a, hipStream_t s, const Marker& mk) {
   // a launch of fewer waves than ~2 per SIMD runs its tokens S lanes each
   // (k_ec_point_split): one wave per SIMD leaves the madd chain's latency bare
   bool launched = false;
-  if (n <= EC_SPLIT_MAX_TOKENS) {
+  const bool small_ok = a.force_point == 0;   // (debugging: k_ec_point at every size)
+  if (small_ok && n <= EC_SPLIT_MAX_TOKENS) {
     hipLaunchKernelGGL((k_ec_point_split<CV, EC_SPLIT, JG_EC_SPLIT_PF != 0>),
                        dim3((unsigned)((n * EC_SPLIT + WAVE - 1) / WAVE)), b, 0, s, a);
     launched = true;
   }
   if constexpr (CV::CLS == jgk::CLS_P256 && EC_SPLIT2_MAX_P256 > 0) {
-    if (!launched && n <= EC_SPLIT2_MAX_P256) {
+    if (small_ok && !launched && n <= EC_SPLIT2_MAX_P256) {
       if (n <= EC_PF_MAX_TOKENS)
         hipLaunchKernelGGL((k_ec_point_split<CV, 2, true>), dim3((unsigned)((n * 2 + WAVE - 1) / WAVE)), b, 0, s, a);
       else
@@ -1253,11 +1284,19 @@ void launch_chain(const EcArgs& a, hipStream_t s, const Marker& mk) {
   // P-521's chain takes 256 VGPRs with the prefetch (one wave per SIMD, 200
   // without): only launches of under ~one wave per SIMD
   constexpr int64_t pf_max = CV::CLS == jgk::CLS_P521 ? std::min<int64_t>(EC_PF_MAX_TOKENS, 65536) : EC_PF_MAX_TOKENS;
-  if (!launched && n <= pf_max) {
+  if (small_ok && !launched && n <= pf_max) {
     hipLaunchKernelGGL((k_ec_point_split<CV, 1, true>), dim3((unsigned)((n + WAVE - 1) / WAVE)), b, 0, s, a);
     launched = true;
   }
-  if (!launched) hipLaunchKernelGGL(k_ec_point<CV>, g, b, 0, s, a);
+  if (!launched) {
+    if constexpr (ec_point_persistent(CV::CLS)) {
+      // at most point_blocks waves share the launch's groups; the debugging
+      // override is taken as it is, more blocks than groups included
+      if (a.point_exact) g.x = (unsigned)a.point_blocks;
+      else if (a.point_blocks > 0) g.x = (unsigned)std::min<int64_t>(waves, a.point_blocks);
+    }
+    hipLaunchKernelGGL(k_ec_point<CV>, g, b, 0, s, a);
+  }
   mk("point");
   if (a.part == EC_FAST) return;
   hipLaunchKernelGGL(k_ec_exact<CV>, dim3(64), b, 0, s, a);
