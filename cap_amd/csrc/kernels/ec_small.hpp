@@ -33,32 +33,6 @@ constexpr uint32_t SM_SIG_CHARS = 176;                            // ES512's 132
 
 __device__ __forceinline__ int sm_hash_bits(int alg) { return alg == 7 ? 256 : alg == 8 ? 384 : 512; }
 
-// x(R) mod n == r for R = (X : Y : Z) Jacobian, Z != 0:
-// X == r Z^2, or r + n < p and X == (r + n) Z^2
-template <class CV>
-__device__ bool ec_x_matches(const uint32_t* X, const uint32_t* Z, const uint32_t* r) {
-  using Fp = typename CV::Fp;
-  using Fn = typename CV::Fn;
-  constexpr int L = Fp::L;
-  uint32_t zz[L], rm[L], tt[L];
-  mp::sqr<Fp>(zz, Z);
-  mp::to_mont<Fp>(rm, r);
-  mp::mul<Fp>(tt, rm, zz);
-  bool ok = mp::eq_mod<Fp>(X, tt);
-  if (!ok) {
-    uint32_t rn[L], pl[L];
-    mp::add<Fp>(rn, r, Fn::M);
-    mp::norm<Fp>(rn);
-    mp::set_const<Fp>(pl, Fp::M);
-    if (lt_limbs<L>(rn, pl)) {
-      mp::to_mont<Fp>(rm, rn);
-      mp::mul<Fp>(tt, rm, zz);
-      ok = mp::eq_mod<Fp>(X, tt);
-    }
-  }
-  return ok;
-}
-
 // One level of the cross-lane combine: lane a (bit `off` clear, "lo") and lane
 // a ^ off ("hi") hold Jacobian partials P_lo, P_hi (normalized coordinates)
 // and split the products of P_lo + P_hi between them (jadd's arithmetic, same

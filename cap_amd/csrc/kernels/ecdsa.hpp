@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "point_form.hpp"
 #include "prep.hpp"
 
 struct EcArgs {
@@ -43,11 +44,10 @@ enum : int32_t { EC_ALL = 0, EC_FAST = 1, EC_EXACT = 2 };
 #ifndef JG_EC_POINT_SLOTS
 #define JG_EC_POINT_SLOTS 4
 #endif
-// The curves whose k_ec_point loops and takes the cap: P-256.  EdDSA + ES384
-// read 302-310 M/s with the P-384 kernel capped against 305-312 without, so
-// P-384 and P-521 keep one block per group and no counter (grp_next and
-// point_blocks are not read for them).
-constexpr bool ec_point_persistent(int cls) { return cls == jgk::CLS_P256; }
+// The curves whose k_ec_point loops and takes the cap: ec_point_persistent
+// (point_form.hpp).  grp_next and point_blocks are not read for the others.
+static_assert(PF_CLS_P256 == jgk::CLS_P256 && PF_CLS_P384 == jgk::CLS_P384 && PF_CLS_P521 == jgk::CLS_P521 &&
+              PF_CLS_ED25519 == jgk::CLS_ED25519, "point_form.hpp numbers the classes as common.hpp does");
 
 // table geometry per curve: words per entry (x,y Montgomery limbs, 16-B aligned)
 constexpr int ec_limbs(int cls) { return cls == jgk::CLS_P256 ? 10 : cls == jgk::CLS_P384 ? 15 : 20; }

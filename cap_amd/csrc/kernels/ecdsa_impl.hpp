@@ -70,8 +70,7 @@ __device__ __forceinline__ bool zero_limbs(const uint32_t* a) {
 }
 
 // ------------------------------------------------------------------ scalar
-// Per-token inputs of the scalar stage, in two halves so the batched kernel
-// can issue one token's loads while it computes the previous one:
+// Per-token inputs of the scalar stage, in two halves:
 // ec_scalar_load reads the raw words (job, status, key validity, r / s words,
 // digest words), ec_scalar_finish checks them and returns ok with r, s, e as
 // plain 28-bit limbs (s replaced by 1 when the token is rejected, so the batch
@@ -164,29 +163,17 @@ __device__ __forceinline__ bool ec_scalar_inputs(const EcArgs& a, int64_t p, uin
   return ec_scalar_finish<CV>(a, p, R, r, s, e);
 }
 
-// Pass 2 of the batched scalar stage (the checks are done): the prefix product
-// c_{j-1}, s_j (Montgomery) and the raw r / e words of token j, loaded one
-// token ahead like pass 1's inputs.
+// Pass 2 of the batched scalar stage (the checks are done, only the values
+// are needed): the raw r / e words of a token that passed ec_scalar_inputs ...
 template <class CV>
 struct ScalarRaw2 {
-  static constexpr int L = CV::Fn::L;
-  uint32_t cprev[L], sm[L];
   uint32_t rw[ScalarRaw<CV>::CW], ew[ScalarRaw<CV>::EW];
 };
 
 template <class CV>
-__device__ __forceinline__ void ec_scalar_load2(const EcArgs& a, int64_t p, int64_t pprev, ScalarRaw2<CV>& R) {
-  using Fn = typename CV::Fn;
-  constexpr int L = Fn::L, CW = ScalarRaw<CV>::CW, EW = ScalarRaw<CV>::EW;
+__device__ __forceinline__ void ec_scalar_load2(const EcArgs& a, int64_t p, ScalarRaw2<CV>& R) {
+  constexpr int CW = ScalarRaw<CV>::CW, EW = ScalarRaw<CV>::EW;
   const int64_t np = a.npad;
-  if (pprev >= 0) {
-#pragma unroll
-    for (int k = 0; k < L; ++k) R.cprev[k] = a.u1w[(int64_t)k * np + pprev];
-  } else {
-    mp::set_const<Fn>(R.cprev, Fn::ONE);
-  }
-#pragma unroll
-  for (int k = 0; k < L; ++k) R.sm[k] = a.u2w[(int64_t)k * np + p];
 #pragma unroll
   for (int q = 0; q < CW; ++q) R.rw[q] = a.sigw[(int64_t)q * np + p];
   const int hw = ec_hash_words<CV>(job_alg(a.jobs[p]));
@@ -197,14 +184,13 @@ __device__ __forceinline__ void ec_scalar_load2(const EcArgs& a, int64_t p, int6
   }
 }
 
-// r and e of a token that passed ec_scalar_inputs (pass 2 of the batched
-// scalar stage: the checks are done, only the values are needed)
+// ... and its r and e as plain limbs
 template <class CV>
 __device__ __forceinline__ void ec_scalar_re(const EcArgs& a, int64_t p, uint32_t* r, uint32_t* e) {
   using Fn = typename CV::Fn;
   constexpr int L = Fn::L;
   ScalarRaw2<CV> R;
-  ec_scalar_load2<CV>(a, p, -1, R);
+  ec_scalar_load2<CV>(a, p, R);
   mp::words_to_limbs<L, ScalarRaw<CV>::CW>(r, R.rw);
   mp::words_to_limbs<L, ScalarRaw<CV>::EW>(e, R.ew);
   mp::csub<Fn>(e);
@@ -241,13 +227,6 @@ __device__ __forceinline__ void store_digit_rows(const EcArgs& a, int64_t p, con
 #ifndef JG_EC_SCALAR_WPB
 #define JG_EC_SCALAR_WPB 4
 #endif
-// JG_EC_SCALAR_PF=1: both passes load the next token's words before computing
-// the current one.  Measured no faster for P-256 (0.189-0.190 vs 0.192 ms per
-// 1 M, profiles/r04_s4/scalar_pf_ab.json) and it costs registers (P-256 138 ->
-// 203 VGPRs, P-384 past 256, P-521 spills), so it is off (A/B knob).
-#ifndef JG_EC_SCALAR_PF
-#define JG_EC_SCALAR_PF 0
-#endif
 constexpr int EC_SCALAR_WPB = JG_EC_SCALAR_WPB;
 // WPB: waves per block sharing one inversion (small launches: 1, launch_chain)
 template <class CV, int WPB = EC_SCALAR_WPB>
@@ -280,57 +259,6 @@ __global__ void __launch_bounds__(64 * WPB) JG_EC_SCALAR_ATTR k_ec_scalar_batch(
   int nb = 0;
   constexpr int WG = ec_comb_w(CV::CLS, true), NG = ec_windows(CV::CLS, true);
   constexpr int WQ = CV::WQ, NQ = ec_windows_w(CV::CLS, CV::WQ);
-#if JG_EC_SCALAR_PF
-  // Both passes load token j+1's (pass 2: j-1's) words before computing token j.
-  {
-    ScalarRaw<CV> cur, nxt;
-    int64_t p = a.begin + i;
-    bool have = B > 0 && i < S && p < a.end;
-    if (have) ec_scalar_load<CV>(a, p, cur);
-    for (int j = 0; have; ++j) {
-      const int64_t pn = p + S;
-      const bool more = j + 1 < B && pn < a.end;
-      if (more) ec_scalar_load<CV>(a, pn, nxt);
-      uint32_t r[L], s[L], e[L], sm[L];
-      const bool ok = ec_scalar_finish<CV>(a, p, cur, r, s, e);
-      if (!ok && job_live(cur.jb)) a.status[p] = ST_REJECT;
-      mp::to_mont<Fn>(sm, s);
-      mp::mul<Fn>(acc, acc, sm);
-#pragma unroll
-      for (int k = 0; k < L; ++k) {
-        a.u1w[(int64_t)k * np + p] = acc[k];
-        a.u2w[(int64_t)k * np + p] = sm[k];
-      }
-      ++nb;
-      if (!more) break;
-      cur = nxt;
-      p = pn;
-    }
-  }
-  uint32_t inv[L];
-  mp::block_inv<Fn, WPB>(inv, acc);
-  if (nb > 0) {
-    ScalarRaw2<CV> cur, nxt;
-    int64_t p = a.begin + i + (int64_t)(nb - 1) * S;
-    ec_scalar_load2<CV>(a, p, nb > 1 ? p - S : -1, cur);
-    for (int j = nb - 1; j >= 0; --j) {
-      if (j > 0) ec_scalar_load2<CV>(a, p - S, j > 1 ? p - 2 * S : -1, nxt);
-      uint32_t w[L], r[L], e[L], u1[L], u2[L];
-      mp::mul<Fn>(w, inv, cur.cprev);              // s_j^-1 R
-      mp::mul<Fn>(inv, inv, cur.sm);
-      mp::words_to_limbs<L, ScalarRaw<CV>::CW>(r, cur.rw);
-      mp::words_to_limbs<L, ScalarRaw<CV>::EW>(e, cur.ew);
-      mp::csub<Fn>(e);
-      mp::mul<Fn>(u1, e, w); mp::csub<Fn>(u1);
-      mp::mul<Fn>(u2, r, w); mp::csub<Fn>(u2);
-      store_digit_rows<CV, WG, NG>(a, p, u1, 0);  // (the rare exact path recomputes u1, u2 itself)
-      store_digit_rows<CV, WQ, NQ>(a, p, u2, NG);
-      if (j == 0) break;
-      cur = nxt;
-      p -= S;
-    }
-  }
-#else
   for (int j = 0; j < B && i < S; ++j) {
     const int64_t p = a.begin + i + (int64_t)j * S;
     if (p >= a.end) break;
@@ -369,7 +297,6 @@ __global__ void __launch_bounds__(64 * WPB) JG_EC_SCALAR_ATTR k_ec_scalar_batch(
     store_digit_rows<CV, WG, NG>(a, p, u1, 0);  // (the rare exact path recomputes u1, u2 itself)
     store_digit_rows<CV, WQ, NQ>(a, p, u2, NG);
   }
-#endif
 }
 
 // ------------------------------------------------------------------ point ops
@@ -547,149 +474,84 @@ __device__ __forceinline__ void store_entry(uint32_t* out, const uint32_t* x, co
   }
 }
 
+// A table entry as loaded, converted at use, so that a chain can hold the next
+// addition's entry in flight: the packed words (P-256) or the 2L limbs
+template <class CV>
+struct RawEnt {
+  static constexpr int NW = ec_packed(CV::CLS) ? 16 : 2 * CV::Fp::L;
+  uint32_t w[NW];
+};
+template <class CV>
+__device__ __forceinline__ void load_ent(RawEnt<CV>& r, const uint32_t* __restrict__ ent) {
+  if constexpr (RawEnt<CV>::NW % 4 == 0) {
+    const uint4* e4 = reinterpret_cast<const uint4*>(ent);
+#pragma unroll
+    for (int i = 0; i < RawEnt<CV>::NW / 4; ++i) {
+      const uint4 q = e4[i];
+      r.w[4 * i] = q.x; r.w[4 * i + 1] = q.y; r.w[4 * i + 2] = q.z; r.w[4 * i + 3] = q.w;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < RawEnt<CV>::NW; ++i) r.w[i] = ent[i];
+  }
+}
+// The accumulator += the entry r for digit d (nothing for d == 0).
 // Z1ONE: the accumulator, if not empty, holds exactly one table entry (Z == 1)
+template <class CV, bool Z1ONE = false>
+__device__ __forceinline__ void add_ent(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty, const RawEnt<CV>& r, int d) {
+  using Fp = typename CV::Fp;
+  constexpr int L = Fp::L;
+  if (d == 0) return;
+  uint32_t x2[L], y2[L];
+  if constexpr (ec_packed(CV::CLS)) {
+    mp::words_to_limbs<L, 8>(x2, r.w);
+    mp::words_to_limbs<L, 8>(y2, r.w + 8);
+  } else {
+#pragma unroll
+    for (int j = 0; j < L; ++j) { x2[j] = r.w[j]; y2[j] = r.w[L + j]; }
+  }
+  if (d < 0) mp::neg<Fp>(y2, y2);
+  if (empty) {
+    mp::copy<Fp>(X, x2);
+    mp::copy<Fp>(Y, y2); mp::freduce<Fp>(Y);
+    mp::set_const<Fp>(Z, Fp::ONE);
+    empty = false;
+  } else if constexpr (Z1ONE) {
+    madd_z1<Fp>(X, Y, Z, x2, y2);
+  } else {
+    madd<Fp>(X, Y, Z, x2, y2);
+  }
+}
+
+// entry |d| of window w of a comb table, loaded and added
 template <class CV, bool GEN, bool Z1ONE = false>
 __device__ __forceinline__ void add_window(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty,
                                            const uint32_t* __restrict__ tab, int w, int d) {
-  using Fp = typename CV::Fp;
-  constexpr int L = Fp::L, STRIDE = ec_stride(CV::CLS), NE = GEN ? ec_entries(CV::CLS, true) : 1 << (CV::WQ - 1);
+  constexpr int STRIDE = ec_stride(CV::CLS), NE = GEN ? ec_entries(CV::CLS, true) : 1 << (CV::WQ - 1);
   if (d == 0) return;
   const int ad = d < 0 ? -d : d;
-  const uint32_t* ent = tab + ((int64_t)w * NE + (ad - 1)) * STRIDE;
-  uint32_t x2[L], y2[L];
-  load_entry<CV>(ent, x2, y2);
-  if (d < 0) mp::neg<Fp>(y2, y2);
-  if (empty) {
-    mp::copy<Fp>(X, x2);
-    mp::copy<Fp>(Y, y2); mp::freduce<Fp>(Y);
-    mp::set_const<Fp>(Z, Fp::ONE);
-    empty = false;
-  } else if constexpr (Z1ONE) {
-    madd_z1<Fp>(X, Y, Z, x2, y2);
-  } else {
-    madd<Fp>(X, Y, Z, x2, y2);
-  }
+  RawEnt<CV> r;
+  load_ent<CV>(r, tab + ((int64_t)w * NE + (ad - 1)) * STRIDE);
+  add_ent<CV, Z1ONE>(X, Y, Z, empty, r, d);
 }
 
-// Packed (P-256) entries as raw words, for the one-entry-ahead loop of
-// k_ec_point (JG_EC_POINT_PF): the loads of the next addition's entry are in
-// flight while the current addition computes.
+// r of token p as plain limbs, from the signature rows
 template <class CV>
-__device__ __forceinline__ void load_raw(const uint32_t* __restrict__ ent, uint4* r) {
-  const uint4* e4 = reinterpret_cast<const uint4*>(ent);
+__device__ __forceinline__ void ec_load_r(const EcArgs& a, int64_t p, uint32_t* r) {
+  constexpr int CW = ec_sig_words(CV::CLS);
+  uint32_t rw[CW];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) r[i] = e4[i];
+  for (int q = 0; q < CW; ++q) rw[q] = a.sigw[(int64_t)q * a.npad + p];
+  mp::words_to_limbs<CV::Fp::L, CW>(r, rw);
 }
-template <class CV, bool Z1ONE = false>
-__device__ __forceinline__ void add_raw(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty, const uint4* r, int d) {
-  using Fp = typename CV::Fp;
-  constexpr int L = Fp::L;
-  if (d == 0) return;
-  const uint32_t wx[8] = {r[0].x, r[0].y, r[0].z, r[0].w, r[1].x, r[1].y, r[1].z, r[1].w};
-  const uint32_t wy[8] = {r[2].x, r[2].y, r[2].z, r[2].w, r[3].x, r[3].y, r[3].z, r[3].w};
-  uint32_t x2[L], y2[L];
-  mp::words_to_limbs<L, 8>(x2, wx);
-  mp::words_to_limbs<L, 8>(y2, wy);
-  if (d < 0) mp::neg<Fp>(y2, y2);
-  if (empty) {
-    mp::copy<Fp>(X, x2);
-    mp::copy<Fp>(Y, y2); mp::freduce<Fp>(Y);
-    mp::set_const<Fp>(Z, Fp::ONE);
-    empty = false;
-  } else if constexpr (Z1ONE) {
-    madd_z1<Fp>(X, Y, Z, x2, y2);
-  } else {
-    madd<Fp>(X, Y, Z, x2, y2);
-  }
-}
-// JG_EC_POINT_PF=1 (P-256 at equal G / key widths): 128 VGPRs, still 4 waves
-// per SIMD, point kernel 1.282-1.288 -> 1.270-1.284 ms per 1 M tokens
-// (profiles/r04_s6/point_pf_ab.json) -- within noise, so off (A/B knob)
-#ifndef JG_EC_POINT_PF
-#define JG_EC_POINT_PF 0
-#endif
 
-// JG_EC_POINT_ATTR: per translation unit, as JG_EC_SCALAR_ATTR (occupancy A/Bs)
-#ifndef JG_EC_POINT_ATTR
-#define JG_EC_POINT_ATTR
-#endif
-// one token of k_ec_point: the comb sum, the x(R) check, the verdict
+// x(R) mod n == r for R = (X : Y : Z) Jacobian, Z != 0:
+// X == r Z^2, or r + n < p and X == (r + n) Z^2
 template <class CV>
-__device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p) {
+__device__ __forceinline__ bool ec_x_matches(const uint32_t* X, const uint32_t* Z, const uint32_t* r) {
   using Fp = typename CV::Fp;
   using Fn = typename CV::Fn;
   constexpr int L = Fp::L;
-  constexpr int NG = ec_windows(CV::CLS, true), NQ = ec_windows_w(CV::CLS, CV::WQ);
-  constexpr int NWIN = NG > NQ ? NG : NQ;
-  const int64_t np = a.npad;
-  const JobDev jb = a.jobs[p];
-  if (!job_live(jb)) return;
-  if (a.status[p] != ST_OK) { a.verdict_pad[p] = 0; return; }
-  const int kidx = __builtin_amdgcn_readfirstlane(job_key(jb));
-  const uint32_t* __restrict__ qtab = key_table(a.keys[kidx]);
-  const uint32_t* __restrict__ gtab = a.gtab;
-
-  uint32_t X[L], Y[L], Z[L];
-  bool empty = true;
-#if JG_EC_POINT_PF
-  if constexpr (ec_packed(CV::CLS) && NG == NQ) {
-    // additions k = 0 .. 2 NG - 1 alternate G window k/2 and Q window k/2;
-    // digit k+2 and entry k+1 are loaded while addition k computes
-    constexpr int NS = 2 * NG, STRIDE = ec_stride(CV::CLS);
-    constexpr int NEG = ec_entries(CV::CLS, true), NEQ = 1 << (CV::WQ - 1);
-    auto dig = [&](int k) { return (int)a.digs[(int64_t)((k & 1) ? NG + (k >> 1) : (k >> 1)) * np + p]; };
-    auto ent = [&](int k, int d) {
-      const int ad = d < 0 ? -d : d;
-      const int64_t idx = ad == 0 ? 0 : ad - 1;          // a zero digit adds nothing (its load is harmless)
-      return (k & 1) ? qtab + ((int64_t)(k >> 1) * NEQ + idx) * STRIDE : gtab + ((int64_t)(k >> 1) * NEG + idx) * STRIDE;
-    };
-    uint4 rc[4], rn[4];
-    int dc = dig(0), dn = dig(1);
-    load_raw<CV>(ent(0, dc), rc);
-    load_raw<CV>(ent(1, dn), rn);
-    int dnn = dig(2);
-    add_raw<CV>(X, Y, Z, empty, rc, dc);                 // window 0: G is an assignment,
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rc[i] = rn[i];
-    dc = dn; dn = dnn;
-    load_raw<CV>(ent(2, dn), rn);
-    dnn = dig(3);
-    add_raw<CV, true>(X, Y, Z, empty, rc, dc);           // so Q adds onto Z == 1
-    for (int k = 2; k < NS; ++k) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rc[i] = rn[i];
-      dc = dn; dn = dnn;
-      if (k + 1 < NS) load_raw<CV>(ent(k + 1, dn), rn);
-      if (k + 2 < NS) dnn = dig(k + 2);
-      add_raw<CV>(X, Y, Z, empty, rc, dc);
-    }
-  } else
-#endif
-  {
-  // window 0 peeled: its G entry is an assignment, so its Q entry adds onto Z == 1
-  add_window<CV, true>(X, Y, Z, empty, gtab, 0, (int)a.digs[p]);
-  add_window<CV, false, true>(X, Y, Z, empty, qtab, 0, (int)a.digs[(int64_t)NG * np + p]);
-  for (int w = 1; w < NWIN; ++w) {
-    if (w < NG) add_window<CV, true>(X, Y, Z, empty, gtab, w, (int)a.digs[(int64_t)w * np + p]);
-    if (w < NQ) add_window<CV, false>(X, Y, Z, empty, qtab, w, (int)a.digs[(int64_t)(NG + w) * np + p]);
-  }
-  }
-  if (empty) { a.verdict_pad[p] = 0; return; }           // R = infinity (unreachable: u2 != 0)
-  uint32_t zc[L];
-  mp::copy<Fp>(zc, Z);
-  mp::canon<Fp>(zc);
-  if (mp::is_zero_canon<Fp>(zc)) {                        // exceptional case: exact recompute
-    const uint32_t idx = atomicAdd(a.exc_count, 1u);
-    a.exc_list[idx] = (int32_t)p;
-    a.status[p] = ST_EXCEPTIONAL;
-    return;
-  }
-  // x(R) mod n == r  <=>  X == r Z^2  or  (r + n < p and X == (r + n) Z^2)
-  constexpr int CW = ec_sig_words(CV::CLS);
-  uint32_t rw[CW], r[L];
-#pragma unroll
-  for (int q = 0; q < CW; ++q) rw[q] = a.sigw[(int64_t)q * np + p];
-  mp::words_to_limbs<L, CW>(r, rw);
   uint32_t zz[L], rm[L], tt[L];
   mp::sqr<Fp>(zz, Z);
   mp::to_mont<Fp>(rm, r);
@@ -706,7 +568,46 @@ __device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p)
       ok = mp::eq_mod<Fp>(X, tt);
     }
   }
-  a.verdict_pad[p] = ok;
+  return ok;
+}
+
+// one token of k_ec_point: the comb sum, the x(R) check, the verdict
+template <class CV>
+__device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p) {
+  using Fp = typename CV::Fp;
+  constexpr int L = Fp::L;
+  constexpr int NG = ec_windows(CV::CLS, true), NQ = ec_windows_w(CV::CLS, CV::WQ);
+  constexpr int NWIN = NG > NQ ? NG : NQ;
+  const int64_t np = a.npad;
+  const JobDev jb = a.jobs[p];
+  if (!job_live(jb)) return;
+  if (a.status[p] != ST_OK) { a.verdict_pad[p] = 0; return; }
+  const int kidx = __builtin_amdgcn_readfirstlane(job_key(jb));
+  const uint32_t* __restrict__ qtab = key_table(a.keys[kidx]);
+  const uint32_t* __restrict__ gtab = a.gtab;
+
+  uint32_t X[L], Y[L], Z[L];
+  bool empty = true;
+  // window 0 peeled: its G entry is an assignment, so its Q entry adds onto Z == 1
+  add_window<CV, true>(X, Y, Z, empty, gtab, 0, (int)a.digs[p]);
+  add_window<CV, false, true>(X, Y, Z, empty, qtab, 0, (int)a.digs[(int64_t)NG * np + p]);
+  for (int w = 1; w < NWIN; ++w) {
+    if (w < NG) add_window<CV, true>(X, Y, Z, empty, gtab, w, (int)a.digs[(int64_t)w * np + p]);
+    if (w < NQ) add_window<CV, false>(X, Y, Z, empty, qtab, w, (int)a.digs[(int64_t)(NG + w) * np + p]);
+  }
+  if (empty) { a.verdict_pad[p] = 0; return; }           // R = infinity (unreachable: u2 != 0)
+  uint32_t zc[L];
+  mp::copy<Fp>(zc, Z);
+  mp::canon<Fp>(zc);
+  if (mp::is_zero_canon<Fp>(zc)) {                        // exceptional case: exact recompute
+    const uint32_t idx = atomicAdd(a.exc_count, 1u);
+    a.exc_list[idx] = (int32_t)p;
+    a.status[p] = ST_EXCEPTIONAL;
+    return;
+  }
+  uint32_t r[L];
+  ec_load_r<CV>(a, p, r);
+  a.verdict_pad[p] = ec_x_matches<CV>(X, Z, r);
 }
 
 // Persistent: each one-wave block takes 64-token groups of [begin, end) from
@@ -721,7 +622,7 @@ __device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p)
 // P-256 only (ec_point_persistent): the P-384 kernel measured no gain under
 // the cap, so P-384 and P-521 keep one block per group.
 template <class CV>
-__global__ void __launch_bounds__(64) JG_EC_POINT_ATTR k_ec_point(EcArgs a) {
+__global__ void __launch_bounds__(64) k_ec_point(EcArgs a) {
   if constexpr (!ec_point_persistent(CV::CLS)) {
     ec_point_token<CV>(a, a.begin + (int64_t)blockIdx.x * WAVE + threadIdx.x);
     return;
@@ -907,60 +808,15 @@ __global__ void __launch_bounds__(64) k_ec_exact(EcArgs a) {
 // S partial chains of NWIN / S additions run side by side, so a token's
 // latency is ~1/S of k_ec_point's plus log2(S) additions; the work per token
 // grows by those additions and the conversions to normalized form.
-// Raw table entry for the prefetching chain: the packed words (P-256) or the
-// 2L limbs, converted at use
-template <class CV>
-struct RawEnt {
-  static constexpr int NW = ec_packed(CV::CLS) ? 16 : 2 * CV::Fp::L;
-  uint32_t w[NW];
-};
-template <class CV>
-__device__ __forceinline__ void load_ent(RawEnt<CV>& r, const uint32_t* __restrict__ ent) {
-  if constexpr (RawEnt<CV>::NW % 4 == 0) {
-    const uint4* e4 = reinterpret_cast<const uint4*>(ent);
-#pragma unroll
-    for (int i = 0; i < RawEnt<CV>::NW / 4; ++i) {
-      const uint4 q = e4[i];
-      r.w[4 * i] = q.x; r.w[4 * i + 1] = q.y; r.w[4 * i + 2] = q.z; r.w[4 * i + 3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < RawEnt<CV>::NW; ++i) r.w[i] = ent[i];
-  }
-}
-template <class CV>
-__device__ __forceinline__ void add_ent(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty, const RawEnt<CV>& r, int d) {
-  using Fp = typename CV::Fp;
-  constexpr int L = Fp::L;
-  if (d == 0) return;
-  uint32_t x2[L], y2[L];
-  if constexpr (ec_packed(CV::CLS)) {
-    mp::words_to_limbs<L, 8>(x2, r.w);
-    mp::words_to_limbs<L, 8>(y2, r.w + 8);
-  } else {
-#pragma unroll
-    for (int j = 0; j < L; ++j) { x2[j] = r.w[j]; y2[j] = r.w[L + j]; }
-  }
-  if (d < 0) mp::neg<Fp>(y2, y2);
-  if (empty) {
-    mp::copy<Fp>(X, x2);
-    mp::copy<Fp>(Y, y2); mp::freduce<Fp>(Y);
-    mp::set_const<Fp>(Z, Fp::ONE);
-    empty = false;
-  } else {
-    madd<Fp>(X, Y, Z, x2, y2);
-  }
-}
-
 // PF (launches of about one wave per SIMD, JG_EC_PF_MAX): the lane's chain
 // of additions runs one table entry and two digits ahead -- addition j
 // computes while entry j + 1 and digit j + 2 load.  With no other wave on the
 // SIMD to switch to, each addition otherwise waited on a digit load and then
-// on the dependent entry gather.
-template <class CV, int S, bool PF = false>
+// on the dependent entry gather.  launch_chain runs three forms (point_form.hpp):
+// <CV, EC_SPLIT, false>, <CV, 2, true> (P-256) and <CV, 1, true>.
+template <class CV, int S, bool PF>
 __global__ void __launch_bounds__(64) k_ec_point_split(EcArgs a) {
   using Fp = typename CV::Fp;
-  using Fn = typename CV::Fn;
   constexpr int L = Fp::L;
   constexpr int NG = ec_windows(CV::CLS, true), NQ = ec_windows_w(CV::CLS, CV::WQ);
   constexpr int NWIN = NG > NQ ? NG : NQ;
@@ -1012,10 +868,10 @@ __global__ void __launch_bounds__(64) k_ec_point_split(EcArgs a) {
         add_ent<CV>(X, Y, Z, empty, rc, dc);
       }
     } else {
-    for (int w = sub; w < NWIN; w += S) {
-      if (w < NG) add_window<CV, true>(X, Y, Z, empty, gtab, w, (int)a.digs[(int64_t)w * np + p]);
-      if (w < NQ) add_window<CV, false>(X, Y, Z, empty, qtab, w, (int)a.digs[(int64_t)(NG + w) * np + p]);
-    }
+      for (int w = sub; w < NWIN; w += S) {
+        if (w < NG) add_window<CV, true>(X, Y, Z, empty, gtab, w, (int)a.digs[(int64_t)w * np + p]);
+        if (w < NQ) add_window<CV, false>(X, Y, Z, empty, qtab, w, (int)a.digs[(int64_t)(NG + w) * np + p]);
+      }
     }
     if (!empty) {
       mp::canon<Fp>(X); mp::canon<Fp>(Y); mp::canon<Fp>(Z);
@@ -1046,29 +902,9 @@ __global__ void __launch_bounds__(64) k_ec_point_split(EcArgs a) {
     return;
   }
   if (P.inf) { a.verdict_pad[p] = 0; return; }    // R = infinity: rejected
-  // x(R) mod n == r  <=>  X == r Z^2  or  (r + n < p and X == (r + n) Z^2)
-  constexpr int CW = ec_sig_words(CV::CLS);
-  uint32_t rw[CW], r[L];
-#pragma unroll
-  for (int q = 0; q < CW; ++q) rw[q] = a.sigw[(int64_t)q * np + p];
-  mp::words_to_limbs<L, CW>(r, rw);
-  uint32_t zz[L], rm[L], tt[L];
-  mp::sqr<Fp>(zz, P.Z);
-  mp::to_mont<Fp>(rm, r);
-  mp::mul<Fp>(tt, rm, zz);
-  bool ok = mp::eq_mod<Fp>(P.X, tt);
-  if (!ok) {
-    uint32_t rn[L], pl[L];
-    mp::add<Fp>(rn, r, Fn::M);
-    mp::norm<Fp>(rn);
-    mp::set_const<Fp>(pl, Fp::M);
-    if (lt_limbs<L>(rn, pl)) {
-      mp::to_mont<Fp>(rm, rn);
-      mp::mul<Fp>(tt, rm, zz);
-      ok = mp::eq_mod<Fp>(P.X, tt);
-    }
-  }
-  a.verdict_pad[p] = ok;
+  uint32_t r[L];
+  ec_load_r<CV>(a, p, r);
+  a.verdict_pad[p] = ec_x_matches<CV>(P.X, P.Z, r);
 }
 
 // ------------------------------------------------------------------ staging
@@ -1193,57 +1029,6 @@ __global__ void k_ec_table_g(uint32_t* tab) {
   table_entry<CV, W>(tab + (int64_t)e * STRIDE, tab + (int64_t)(e / NE) * NE * STRIDE, e % NE + 1);
 }
 
-// Launches of up to EC_SPLIT_MAX_TOKENS padded tokens run k_ec_point_split
-// with EC_SPLIT lanes per token.  Measured (profiles/r05_s2/split_ab/): a lone
-// ES256 batch of 1 ... 4096 tokens 238 -> 183 us (4 lanes; 2 lanes: 198 us),
-// 16 coalesced single-token callers 45 k -> 60 k calls/s; but the configs[4]
-// classes (62.5 k tokens per launch) ran slower split (P-256 point 0.31 ->
-// 0.26 of the MAD roofline at 4 lanes, P-384 0.40 -> 0.31; 2 lanes: P-256 0.34,
-// P-384 0.38, the batch 82.1 -> 81.2 M/s), so only small launches split.
-#ifndef JG_EC_SPLIT
-#define JG_EC_SPLIT 4
-#endif
-#ifndef JG_EC_SCALAR_SOLO_MAX
-#define JG_EC_SCALAR_SOLO_MAX 16384
-#endif
-constexpr int64_t EC_SCALAR_SOLO_MAX = JG_EC_SCALAR_SOLO_MAX;   // launches up to this size: k_ec_scalar_batch<CV, 1>
-#ifndef JG_EC_SPLIT_MAX
-#define JG_EC_SPLIT_MAX 16384
-#endif
-// P-256 launches of 16 k ... JG_EC_SPLIT2_P256 tokens run two lanes per token
-// (round 5: point 0.30 -> 0.34-0.35 of the MAD roofline at configs[4],
-// profiles/r05_s2/q_ab/), with the prefetch (PF below).  On one key at W = 24
-// the one-lane PF chain was faster (62 k tokens 0.1325 -> 0.1046 ms,
-// profiles/r06_s16/pf3.txt), but in configs[4] -- four keys at W = 26, 86 GB
-// of key tables, so slower gathers -- the class took 0.161 ms one-lane
-// against 0.153 two-lane (profiles/r06_s17 vs r06_s16/cfg_head.json): the
-// second wave per SIMD hides more of the gather than one entry of prefetch.
-#ifndef JG_EC_SPLIT2_P256
-#define JG_EC_SPLIT2_P256 131072
-#endif
-constexpr int64_t EC_SPLIT2_MAX_P256 = JG_EC_SPLIT2_P256;
-// Launches above the split sizes and up to JG_EC_PF_MAX padded tokens (a
-// mixed batch's EC classes, ~1-4 waves per SIMD) run the prefetching chain:
-// k_ec_point_split<CV, 2, true> for P-256 up to EC_SPLIT2_MAX_P256, <CV, 1,
-// true> otherwise (one lane per token, as k_ec_point)
-// (262 k-token launches: P-256 point 0.3467 -> 0.3428 ms, P-384 1.150 ->
-// 1.146 ms with it, profiles/r06_s16/pf4.txt; the 1 M headline launch keeps
-// k_ec_point and its four waves per SIMD)
-#ifndef JG_EC_PF_MAX
-#define JG_EC_PF_MAX 262144
-#endif
-constexpr int64_t EC_PF_MAX_TOKENS = JG_EC_PF_MAX;
-// JG_EC_SPLIT_PF: the prefetching chain in the small-launch split too (lone
-// ES256 chain batches of 256 / 2048 / 8000 tokens: p50 163 -> 157, 182 -> 179,
-// 269 -> 267 us; profiles/r06_s20/pf5.txt).  Off: the two-slot multi-device
-// leg, whose chunk ramp starts with split-size launches, read 105.6 / 98.3 /
-// 79.7 M/s with it against 104.5-106.4 without (profiles/r06_s20/md_ab.txt)
-#ifndef JG_EC_SPLIT_PF
-#define JG_EC_SPLIT_PF 0
-#endif
-constexpr int EC_SPLIT = JG_EC_SPLIT;                    // lanes per token of k_ec_point_split
-constexpr int64_t EC_SPLIT_MAX_TOKENS = JG_EC_SPLIT_MAX;  // launches up to this many padded tokens use it
-
 template <class CV>
 void launch_chain(const EcArgs& a, hipStream_t s, const Marker& mk) {
   const int64_t waves = (a.end - a.begin) / WAVE;
@@ -1263,33 +1048,19 @@ void launch_chain(const EcArgs& a, hipStream_t s, const Marker& mk) {
     hipLaunchKernelGGL(k_ec_scalar_batch<CV>, dim3(sh.grid), dim3(WAVE * EC_SCALAR_WPB), 0, s, a, sh.B);
   }
   mk("scalar");
-  // a launch of fewer waves than ~2 per SIMD runs its tokens S lanes each
-  // (k_ec_point_split): one wave per SIMD leaves the madd chain's latency bare
-  bool launched = false;
-  const bool small_ok = a.force_point == 0;   // (debugging: k_ec_point at every size)
-  if (small_ok && n <= EC_SPLIT_MAX_TOKENS) {
-    hipLaunchKernelGGL((k_ec_point_split<CV, EC_SPLIT, JG_EC_SPLIT_PF != 0>),
-                       dim3((unsigned)((n * EC_SPLIT + WAVE - 1) / WAVE)), b, 0, s, a);
-    launched = true;
-  }
-  if constexpr (CV::CLS == jgk::CLS_P256 && EC_SPLIT2_MAX_P256 > 0) {
-    if (small_ok && !launched && n <= EC_SPLIT2_MAX_P256) {
-      if (n <= EC_PF_MAX_TOKENS)
-        hipLaunchKernelGGL((k_ec_point_split<CV, 2, true>), dim3((unsigned)((n * 2 + WAVE - 1) / WAVE)), b, 0, s, a);
-      else
-        hipLaunchKernelGGL((k_ec_point_split<CV, 2>), dim3((unsigned)((n * 2 + WAVE - 1) / WAVE)), b, 0, s, a);
-      launched = true;
-    }
-  }
-  // P-521's chain takes 256 VGPRs with the prefetch (one wave per SIMD, 200
-  // without): only launches of under ~one wave per SIMD
-  constexpr int64_t pf_max = CV::CLS == jgk::CLS_P521 ? std::min<int64_t>(EC_PF_MAX_TOKENS, 65536) : EC_PF_MAX_TOKENS;
-  if (small_ok && !launched && n <= pf_max) {
-    hipLaunchKernelGGL((k_ec_point_split<CV, 1, true>), dim3((unsigned)((n + WAVE - 1) / WAVE)), b, 0, s, a);
-    launched = true;
-  }
-  if (!launched) {
-    if constexpr (ec_point_persistent(CV::CLS)) {
+  // the point kernel by launch size (point_form.hpp): a launch of fewer waves
+  // than ~2 per SIMD runs its tokens S lanes each, as one wave per SIMD leaves
+  // the madd chain's latency bare
+  const PointForm f = ec_point_form(CV::CLS, n, a.force_point != 0);
+  const dim3 gs((unsigned)((n * f.lanes + WAVE - 1) / WAVE));
+  if (f.lanes == EC_SPLIT && !f.prefetch) {
+    hipLaunchKernelGGL((k_ec_point_split<CV, EC_SPLIT, false>), gs, b, 0, s, a);
+  } else if (f.lanes == 2) {
+    if constexpr (CV::CLS == jgk::CLS_P256) hipLaunchKernelGGL((k_ec_point_split<CV, 2, true>), gs, b, 0, s, a);
+  } else if (f.prefetch) {
+    hipLaunchKernelGGL((k_ec_point_split<CV, 1, true>), gs, b, 0, s, a);
+  } else {
+    if (f.persistent) {
       // at most point_blocks waves share the launch's groups; the debugging
       // override is taken as it is, more blocks than groups included
       if (a.point_exact) g.x = (unsigned)a.point_blocks;

@@ -14,12 +14,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 #include "ed25519.hpp"
 #include "fe25519.hpp"
 #include "inv_shape.hpp"
 #include "mp.hpp"
+#include "point_form.hpp"
 #include "tables.hpp"
 #include "small_common.hpp"
 
@@ -75,9 +77,6 @@ struct EPt { uint32_t X[L], Y[L], Z[L], T[L]; };
 // convert at the boundary (entries are stored canonical in radix 2^25.5).
 struct FPt { uint32_t X[fe::L], Y[fe::L], Z[fe::L], T[fe::L]; };
 
-#ifndef JG_ED_SHARE_PRE
-#define JG_ED_SHARE_PRE 0
-#endif
 // extended + Niels (y+x, y-x, 2dxy) affine -> extended (complete, a = -1):
 // 7 products.  fe::mul's second operand carries the factor 19 and must be the
 // smaller one: the point side for A, B, C, then E and G (tools/fe25519_bounds.py)
@@ -90,16 +89,7 @@ __device__ __forceinline__ void add_niels(FPt& P, const uint32_t* ypx, const uin
   fe::sub(t, P.Y, P.X); fe::mul(A, ymx, t);
   fe::add(t, P.Y, P.X); fe::mul(B, ypx, t);
   fe::sub(E, B, A); fe::add(H, B, A);
-#if JG_ED_SHARE_PRE
-  // E and G are the g side of two products each, F and H the f side: their
-  // operand forms are prepared once
-  uint32_t e19[fe::L], g19[fe::L], f2[fe::L], h2[fe::L];
-  fe::pre_g(e19, E); fe::pre_g(g19, G); fe::pre_f(f2, F); fe::pre_f(h2, H);
-  fe::mul_pre(P.X, F, f2, E, e19); fe::mul_pre(P.T, H, h2, E, e19);
-  fe::mul_pre(P.Y, H, h2, G, g19); fe::mul_pre(P.Z, F, f2, G, g19);
-#else
   fe::mul(P.X, F, E); fe::mul(P.T, H, E); fe::mul(P.Y, H, G); fe::mul(P.Z, F, G);
-#endif
 }
 
 // extended + extended in radix 2^25.5 (complete, a = -1; add-2008-hwcd-3 with
@@ -150,29 +140,6 @@ __device__ void add_full(EPt& R, const EPt& P, const EPt& Q) {
   mp::mul<Fp>(R.X, E, F); mp::mul<Fp>(R.Y, G, H); mp::mul<Fp>(R.T, E, H); mp::mul<Fp>(R.Z, F, G);
 }
 
-template <int NE>
-__device__ __forceinline__ void add_window(FPt& P, const uint32_t* __restrict__ tab, int w, int d) {
-  if (d == 0) return;
-  const int ad = d < 0 ? -d : d;
-  const uint32_t* ent = tab + ((int64_t)w * NE + (ad - 1)) * ED_STRIDE;
-  uint32_t ypx[fe::L], ymx[fe::L], t2d[fe::L];
-#pragma unroll
-  for (int j = 0; j < fe::L; ++j) { ypx[j] = ent[j]; ymx[j] = ent[fe::L + j]; t2d[j] = ent[2 * fe::L + j]; }
-  // -(x, y) = (-x, y): swap y+x / y-x and negate 2dxy -- selected per lane, so
-  // the wave runs ONE addition (a branch on the digit's sign made lanes of
-  // both signs execute both inlined copies of add_niels)
-  const bool neg = d < 0;
-  uint32_t a1[fe::L], a2[fe::L], nt[fe::L];
-  fe::neg(nt, t2d);
-#pragma unroll
-  for (int j = 0; j < fe::L; ++j) {
-    a1[j] = neg ? ymx[j] : ypx[j];
-    a2[j] = neg ? ypx[j] : ymx[j];
-    t2d[j] = neg ? nt[j] : t2d[j];
-  }
-  add_niels(P, a1, a2, t2d);
-}
-
 // signed W-bit digits d_w in [-2^(W-1), 2^(W-1)], s = sum d_w 2^(W w);
 // digit w goes to dg[w * stride] (k_ed_point: the wave's LDS digit rows)
 template <int W, int NWIN>
@@ -190,30 +157,34 @@ __device__ __forceinline__ void recode(int* dg, const uint32_t* s, int stride = 
   }
 }
 
-// JG_ED_POINT_ATTR: occupancy.  With fe::mul's asm columns the compiler takes
-// 129-132 VGPRs (3 waves per SIMD); capped at 4 waves it spills 5 registers
-// and runs 1 % faster (1 M EdDSA tokens at W = 24: 0.874 -> 0.866 ms, HEAD's
-// C++ columns 0.917 ms, profiles/r06_s2/ed_ab.json).  Round 4: with the C++
-// columns at ~141 VGPRs the same cap cost 4 % (profiles/r04_s6/).
-#ifndef JG_ED_POINT_ATTR
-#define JG_ED_POINT_ATTR __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 // One Niels addition of the table entry at e (30 words: y+x, y-x, 2dxy) for
-// digit d, from registers (k_ed_point's prefetching loop)
+// digit d, from registers
 __device__ __forceinline__ void add_entry(FPt& P, const uint32_t* e, int d) {
   if (d == 0) return;
   const bool neg = d < 0;
   uint32_t a1[fe::L], a2[fe::L], nt[fe::L], t2d[fe::L];
-#pragma unroll
-  for (int j = 0; j < fe::L; ++j) t2d[j] = e[2 * fe::L + j];
-  fe::neg(nt, t2d);
+  fe::neg(nt, e + 2 * fe::L);
 #pragma unroll
   for (int j = 0; j < fe::L; ++j) {
+    // -(x, y) = (-x, y): swap y+x / y-x and negate 2dxy -- selected per lane, so
+    // the wave runs ONE addition (a branch on the digit's sign made lanes of
+    // both signs execute both inlined copies of add_niels)
     a1[j] = neg ? e[fe::L + j] : e[j];
     a2[j] = neg ? e[j] : e[fe::L + j];
-    t2d[j] = neg ? nt[j] : t2d[j];
+    t2d[j] = neg ? nt[j] : e[2 * fe::L + j];
   }
   add_niels(P, a1, a2, t2d);
+}
+
+// entry |d| of window w of a comb table of ne entries per window, loaded and added
+__device__ __forceinline__ void add_window(FPt& P, const uint32_t* __restrict__ tab, int ne, int w, int d) {
+  if (d == 0) return;
+  const int ad = d < 0 ? -d : d;
+  const uint32_t* ent = tab + ((int64_t)w * ne + (ad - 1)) * ED_STRIDE;
+  uint32_t e[3 * fe::L];
+#pragma unroll
+  for (int j = 0; j < fe::L; ++j) { e[j] = ent[j]; e[fe::L + j] = ent[fe::L + j]; e[2 * fe::L + j] = ent[2 * fe::L + j]; }
+  add_entry(P, e, d);
 }
 
 // 30 words of a table entry as 7 x 16 B + 8 B loads
@@ -244,11 +215,17 @@ __device__ __forceinline__ void ed_point_body(const EdArgs& a) {
   const int kidx = __builtin_amdgcn_readfirstlane(job_key(jb));
   const DevKey& K = a.keys[kidx];
   bool ok = a.status[p] == ST_OK && K.valid && a.siglen[p] == 64;
+  constexpr int NB = ed_windows(true), NA = ed_windows_w(WA), NW = NB > NA ? NB : NA;
+  // the signed digits of S (B windows) and k (-A windows) wait in LDS, one row
+  // per window, lane-contiguous (conflict-free): held in registers they took
+  // NB + NA VGPRs through the whole loop and the kernel three waves per SIMD
+  __shared__ int dg[(NB + NA) * WAVE];
+  const int lane = (int)threadIdx.x;
   // S: canonical, and sig[63] & 0xE0 == 0
-  uint32_t sw[8], s[L];
+  uint32_t sw[8], sc[L];
 #pragma unroll
   for (int q = 0; q < 8; ++q) sw[q] = a.sigw[(int64_t)(8 + q) * np + p];
-  const bool sok = ed_s_ok(s, sw);
+  const bool sok = ed_s_ok(sc, sw);
   ok = ok && sok;
   // k = H mod L  (H little-endian, 512 bits)
   uint32_t k[L];
@@ -261,13 +238,7 @@ __device__ __forceinline__ void ed_point_body(const EdArgs& a) {
     }
     ed_k_mod_l(k, hw);
   }
-  constexpr int NB = ed_windows(true), NA = ed_windows_w(WA), NW = NB > NA ? NB : NA;
-  // the signed digits of S (B windows) and k (-A windows) wait in LDS, one row
-  // per window, lane-contiguous (conflict-free): held in registers they took
-  // NB + NA VGPRs through the whole loop and the kernel three waves per SIMD
-  __shared__ int dg[(NB + NA) * WAVE];
-  const int lane = (int)threadIdx.x;
-  recode<ed_comb_w(true), NB>(dg + lane, s, WAVE);
+  recode<ed_comb_w(true), NB>(dg + lane, sc, WAVE);
   recode<WA, NA>(dg + NB * WAVE + lane, k, WAVE);
   FPt P;                                      // the neutral element (0, 1, 1, 0)
   fe::set_small(P.X, 0u); fe::set_small(P.Y, 1u); fe::set_small(P.Z, 1u); fe::set_small(P.T, 0u);
@@ -301,13 +272,13 @@ __device__ __forceinline__ void ed_point_body(const EdArgs& a) {
     }
   } else {
 #pragma unroll 1
-  for (int w = 0; w < NW; ++w) {
-    // each lane reads back only its own digits: no barrier needed
-    const int e1 = w < NB ? dg[w * WAVE + lane] : 0;
-    const int e2 = w < NA ? dg[(NB + w) * WAVE + lane] : 0;
-    add_window<ed_entries(true)>(P, a.btab, w, e1);
-    add_window<(1 << (WA - 1))>(P, atab, w, e2);
-  }
+    for (int w = 0; w < NW; ++w) {
+      // each lane reads back only its own digits: no barrier needed
+      const int e1 = w < NB ? dg[w * WAVE + lane] : 0;
+      const int e2 = w < NA ? dg[(NB + w) * WAVE + lane] : 0;
+      add_window(P, a.btab, ed_entries(true), w, e1);
+      add_window(P, atab, 1 << (WA - 1), w, e2);
+    }
   }
 #pragma unroll
   for (int j = 0; j < fe::L; ++j) {                // radix-2^25.5 limbs (k_ed_finish converts)
@@ -318,15 +289,16 @@ __device__ __forceinline__ void ed_point_body(const EdArgs& a) {
   if (!ok) a.status[p] = ST_REJECT;
 }
 
+// Occupancy.  k_ed_point and k_ed_point_split: with fe::mul's asm columns the
+// compiler takes 129-132 VGPRs (3 waves per SIMD); capped at 4 waves it spills
+// 5 registers and runs 1 % faster (profiles/r06_s2/ed_ab.json).
+// k_ed_point_pf holds an entry in flight and runs where few waves are resident.
 template <int WA>
-__global__ void __launch_bounds__(64) JG_ED_POINT_ATTR k_ed_point(EdArgs a) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_ed_point(EdArgs a) {
   ed_point_body<WA, false>(a);
 }
-#ifndef JG_ED_POINT_PF_ATTR
-#define JG_ED_POINT_PF_ATTR __attribute__((amdgpu_waves_per_eu(2)))
-#endif
 template <int WA>
-__global__ void __launch_bounds__(64) JG_ED_POINT_PF_ATTR k_ed_point_pf(EdArgs a) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_ed_point_pf(EdArgs a) {
   ed_point_body<WA, true>(a);
 }
 
@@ -338,10 +310,8 @@ __global__ void __launch_bounds__(64) JG_ED_POINT_PF_ATTR k_ed_point_pf(EdArgs a
 // the sum.  A token's latency falls to about 2/S of k_ed_point's for
 // log2(S) extra additions on its path (S - 1 in all).  The B-side lanes check
 // S, the A-side lanes derive k = H mod L.
-// PF: the lane's next table entry loads while its current addition computes
-// (as k_ed_point_pf)
-template <int WA, int S, bool PF = false>
-__global__ void __launch_bounds__(64) JG_ED_POINT_ATTR k_ed_point_split(EdArgs a) {
+template <int WA, int S>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_ed_point_split(EdArgs a) {
   static_assert(S == 2 || S == 4, "two or four lanes per token");
   constexpr int H = S / 2;                        // lanes per scalar
   const int lane = (int)threadIdx.x, sub = lane % S, side = sub / H, par = sub % H;
@@ -384,48 +354,9 @@ __global__ void __launch_bounds__(64) JG_ED_POINT_ATTR k_ed_point_split(EdArgs a
   if (live) {
     const uint32_t* __restrict__ tab = side ? key_table(K) : a.btab;
     const int ne = side ? (1 << (WA - 1)) : ed_entries(true);
-    if constexpr (PF) {
-      // step i: window par + H i (rows past the scalar's windows hold digit 0)
-      const int nst = par < NW ? (NW - par + H - 1) / H : 0;
-      auto entry = [&](int i, int d) {
-        const int ad = d < 0 ? -d : d;
-        const int w = ad ? par + H * i : 0;           // a zero digit loads window 0's first entry (unused)
-        return tab + ((int64_t)w * ne + (ad ? ad - 1 : 0)) * ED_STRIDE;
-      };
-      EdEnt rn;
-      int dn = nst > 0 ? dg[par * WAVE + lane] : 0;
-      if (nst > 0) load_ent(rn, entry(0, dn));
 #pragma unroll 1
-      for (int i = 0; i < nst; ++i) {
-        uint32_t e[30];
-        ent_words(e, rn);
-        const int dc = dn;
-        if (i + 1 < nst) {
-          dn = dg[(par + H * (i + 1)) * WAVE + lane];
-          load_ent(rn, entry(i + 1, dn));
-        }
-        add_entry(P, e, dc);
-      }
-    } else
-#pragma unroll 1
-    for (int w = par; w < NW; w += H) {
-      const int d = dg[w * WAVE + lane];        // this lane's own digit row: no barrier needed
-      if (d == 0) continue;
-      const int ad = d < 0 ? -d : d;
-      const uint32_t* ent = tab + ((int64_t)w * ne + (ad - 1)) * ED_STRIDE;
-      uint32_t ypx[fe::L], ymx[fe::L], t2d[fe::L], a1[fe::L], a2[fe::L], nt[fe::L];
-#pragma unroll
-      for (int j = 0; j < fe::L; ++j) { ypx[j] = ent[j]; ymx[j] = ent[fe::L + j]; t2d[j] = ent[2 * fe::L + j]; }
-      const bool neg = d < 0;
-      fe::neg(nt, t2d);
-#pragma unroll
-      for (int j = 0; j < fe::L; ++j) {
-        a1[j] = neg ? ymx[j] : ypx[j];
-        a2[j] = neg ? ypx[j] : ymx[j];
-        t2d[j] = neg ? nt[j] : t2d[j];
-      }
-      add_niels(P, a1, a2, t2d);
-    }
+    for (int w = par; w < NW; w += H)             // this lane's own digit rows: no barrier needed
+      add_window(P, tab, ne, w, dg[w * WAVE + lane]);
   }
   // the partner lane's partial (and verdict); every lane of the wave joins
   auto partner = [&](FPt& Q, int off) {
@@ -641,8 +572,8 @@ __global__ void __launch_bounds__(SM_THREADS) k_ed_small(EdSmallArgs a) {
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       const int w = lane + S * i;
-      if (w < NB) add_window<ed_entries(true)>(P, a.btab, w, dg[w]);
-      if (w < NA) add_window<(1 << (WA - 1))>(P, atab, w, dg[NB + w]);
+      if (w < NB) add_window(P, a.btab, ed_entries(true), w, dg[w]);
+      if (w < NA) add_window(P, atab, 1 << (WA - 1), w, dg[NB + w]);
     }
   }
   // partials of lanes 0..15 added pairwise with the complete law (every lane joins the shuffles)
@@ -844,88 +775,38 @@ __global__ void k_ed_table_keys(const DevKey* keys, uint32_t* blob, const int32_
   table_entry<W>(tab + (int64_t)e * ED_STRIDE, tab + (int64_t)(e / NE) * NE * ED_STRIDE, e % NE + 1);
 }
 
-}  // namespace
-
-// Measured (profiles/r05_s2/q_ab/, ed_split_ab/, r05_s7/ed4_ab/): a lone
-// EdDSA batch of 1 ... 4096 tokens 210-244 -> 182-218 us with two lanes and
-// 5-12 us less again with four; configs[4]'s 38 k-token Ed25519 launch
-// unchanged with two lanes (0.081 ms either way) and slower with four (0.083
-// -> 0.110 ms), so only small launches split (JG_ED_SPLIT4_MAX: A/B knob).
-#ifndef JG_ED_SPLIT_MAX
-#define JG_ED_SPLIT_MAX 16384
-#endif
-#ifndef JG_ED_SPLIT_LANES
-#define JG_ED_SPLIT_LANES 4
-#endif
-#ifndef JG_ED_SPLIT4_MAX
-#define JG_ED_SPLIT4_MAX 0
-#endif
-// JG_ED_SPLIT_PF: the prefetching loop in the small-launch split too (lone
-// EdDSA chain batches of 256 / 8000 tokens: p50 156 -> 154, 240 -> 229 us;
-// 2048: 174 -> 177; profiles/r06_s20/pf5.txt).  Off with JG_EC_SPLIT_PF
-// (ecdsa_impl.hpp)
-#ifndef JG_ED_SPLIT_PF
-#define JG_ED_SPLIT_PF 0
-#endif
-constexpr int64_t ED_SPLIT_MAX_TOKENS = JG_ED_SPLIT_MAX;  // launches up to this many padded tokens: k_ed_point_split
-constexpr int64_t ED_SPLIT4_MAX_TOKENS = JG_ED_SPLIT4_MAX;  // ... with 4 lanes per token above ED_SPLIT_MAX_TOKENS
-// launches up to this many padded tokens (above the split sizes): k_ed_point_pf
-#ifndef JG_ED_PF_MAX
-#define JG_ED_PF_MAX 131072
-#endif
-constexpr int64_t ED_PF_MAX_TOKENS = JG_ED_PF_MAX;
-// ... and up to this many: two lanes per token (k_ed_point_split<2, true>).
-// A/B knob, off: at configs[4]'s 38912-token class it ran 0.089 ms against
-// k_ed_point_pf's 0.069 (profiles/r06_s16/pf2.txt)
-#ifndef JG_ED_SPLIT2_PF_MAX
-#define JG_ED_SPLIT2_PF_MAX 0
-#endif
-constexpr int64_t ED_SPLIT2_PF_MAX_TOKENS = JG_ED_SPLIT2_PF_MAX;
-
-template <int S, bool PF = false>
-void launch_ed_split(const EdArgs& a, int64_t waves, hipStream_t s) {
-  dim3 g((unsigned)(S * waves)), b(WAVE);
-  switch (a.wa) {
-    case 24: hipLaunchKernelGGL((k_ed_point_split<24, S, PF>), g, b, 0, s, a); break;
-    case 22: hipLaunchKernelGGL((k_ed_point_split<22, S, PF>), g, b, 0, s, a); break;
-    case 20: hipLaunchKernelGGL((k_ed_point_split<20, S, PF>), g, b, 0, s, a); break;
-    case 18: hipLaunchKernelGGL((k_ed_point_split<18, S, PF>), g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_ed_point_split<16, S, PF>), g, b, 0, s, a); break;
+// f(std::integral_constant<int, W>) for the key-table width wa of a launch
+// (ed25519.hpp ED_WA; an unknown width runs the narrowest)
+template <class F>
+void with_wa(int wa, F&& f) {
+  switch (wa) {
+    case 24: f(std::integral_constant<int, 24>{}); break;
+    case 22: f(std::integral_constant<int, 22>{}); break;
+    case 20: f(std::integral_constant<int, 20>{}); break;
+    case 18: f(std::integral_constant<int, 18>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
   }
 }
 
+}  // namespace
+
 void launch_ed(const EdArgs& a, hipStream_t s, const Marker& mk) {
-  const int64_t waves = (a.end - a.begin) / WAVE;
-  if (waves <= 0) return;
-  dim3 g((unsigned)waves), b(WAVE);
-  if (a.end - a.begin <= ED_SPLIT_MAX_TOKENS) {
-    // a launch of fewer waves than ~2 per SIMD: S lanes per token
-    launch_ed_split<JG_ED_SPLIT_LANES, JG_ED_SPLIT_PF != 0>(a, waves, s);
-  } else if (a.end - a.begin <= ED_SPLIT4_MAX_TOKENS) {
-    launch_ed_split<4>(a, waves, s);
-  } else if (a.end - a.begin <= ED_SPLIT2_PF_MAX_TOKENS) {
-    launch_ed_split<2, true>(a, waves, s);
-  } else if (a.end - a.begin <= ED_PF_MAX_TOKENS) {
-    switch (a.wa) {
-      case 24: hipLaunchKernelGGL(k_ed_point_pf<24>, g, b, 0, s, a); break;
-      case 22: hipLaunchKernelGGL(k_ed_point_pf<22>, g, b, 0, s, a); break;
-      case 20: hipLaunchKernelGGL(k_ed_point_pf<20>, g, b, 0, s, a); break;
-      case 18: hipLaunchKernelGGL(k_ed_point_pf<18>, g, b, 0, s, a); break;
-      default: hipLaunchKernelGGL(k_ed_point_pf<16>, g, b, 0, s, a); break;
-    }
-  } else {
-  switch (a.wa) {
-    case 24: hipLaunchKernelGGL(k_ed_point<24>, g, b, 0, s, a); break;
-    case 22: hipLaunchKernelGGL(k_ed_point<22>, g, b, 0, s, a); break;
-    case 20: hipLaunchKernelGGL(k_ed_point<20>, g, b, 0, s, a); break;
-    case 18: hipLaunchKernelGGL(k_ed_point<18>, g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL(k_ed_point<16>, g, b, 0, s, a); break;
-  }
-  }
+  const int64_t n = a.end - a.begin;
+  if (n < WAVE) return;
+  // the point kernel by launch size (point_form.hpp): a launch of fewer waves
+  // than ~2 per SIMD runs ED_SPLIT lanes per token
+  const PointForm f = ed_point_form(n);
+  const dim3 g((unsigned)(n * f.lanes / WAVE)), b(WAVE);
+  with_wa(a.wa, [&](auto wa) {
+    constexpr int WA = decltype(wa)::value;
+    if (f.lanes > 1) hipLaunchKernelGGL((k_ed_point_split<WA, ED_SPLIT>), g, b, 0, s, a);
+    else if (f.prefetch) hipLaunchKernelGGL(k_ed_point_pf<WA>, g, b, 0, s, a);
+    else hipLaunchKernelGGL(k_ed_point<WA>, g, b, 0, s, a);
+  });
   mk("point");
   // tokens per thread for the batched inversion (inv_shape.hpp; every launch
   // runs ED_FINISH_WPB waves per block)
-  const InvShape sh = inv_shape(a.end - a.begin, ED_FINISH_WPB, 0);
+  const InvShape sh = inv_shape(n, ED_FINISH_WPB, 0);
   hipLaunchKernelGGL(k_ed_finish, dim3(sh.grid), dim3(WAVE * ED_FINISH_WPB), 0, s, a, sh.B);
   mk("finish");
 }
@@ -948,13 +829,7 @@ void launch_ed_keyprep(DevKey* keys, uint32_t* blob, const int32_t* idx, int n, 
 
 void launch_ed_keytables(int wa, DevKey* keys, uint32_t* blob, const int32_t* tidx, int tn, hipStream_t s, bool sliced) {
   if (tn <= 0) return;
-  switch (wa) {
-    case 24: ed_tables<24>(keys, blob, tidx, tn, s, sliced); break;
-    case 22: ed_tables<22>(keys, blob, tidx, tn, s, sliced); break;
-    case 20: ed_tables<20>(keys, blob, tidx, tn, s, sliced); break;
-    case 18: ed_tables<18>(keys, blob, tidx, tn, s, sliced); break;
-    default: ed_tables<16>(keys, blob, tidx, tn, s, sliced); break;
-  }
+  with_wa(wa, [&](auto w) { ed_tables<decltype(w)::value>(keys, blob, tidx, tn, s, sliced); });
 }
 
 void launch_ed_btable(uint32_t* tab, hipStream_t s) {
@@ -966,11 +841,5 @@ void launch_ed_btable(uint32_t* tab, hipStream_t s) {
 void launch_ed_small(int wa, const EdSmallArgs& a, hipStream_t s) {
   if (a.n == 0) return;
   dim3 g(a.n), b(SM_THREADS);
-  switch (wa) {
-    case 24: hipLaunchKernelGGL(k_ed_small<24>, g, b, 0, s, a); break;
-    case 22: hipLaunchKernelGGL(k_ed_small<22>, g, b, 0, s, a); break;
-    case 20: hipLaunchKernelGGL(k_ed_small<20>, g, b, 0, s, a); break;
-    case 18: hipLaunchKernelGGL(k_ed_small<18>, g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL(k_ed_small<16>, g, b, 0, s, a); break;
-  }
+  with_wa(wa, [&](auto w) { hipLaunchKernelGGL(k_ed_small<decltype(w)::value>, g, b, 0, s, a); });
 }

@@ -76,6 +76,16 @@ extern "C" int tk_ec_scalar_shape(int64_t n, int* B, int64_t* S, int* wpb, unsig
   return 0;
 }
 
+// The point kernel launch_chain (cls = CLS_P256 .. CLS_P521; force: its
+// debugging switch) or launch_ed (CLS_ED25519) picks for a width run of n
+// padded tokens (kernels/point_form.hpp).  Returns 0; -1 on a bad argument.
+extern "C" int tk_point_form(int cls, int64_t n, int force, int* lanes, int* prefetch, int* persistent) {
+  if (cls < CLS_P256 || cls > CLS_ED25519 || n <= 0 || n % WAVE != 0 || !lanes || !prefetch || !persistent) return -1;
+  const PointForm f = cls == CLS_ED25519 ? ed_point_form(n) : ec_point_form(cls, n, force != 0);
+  *lanes = f.lanes; *prefetch = f.prefetch; *persistent = f.persistent;
+  return 0;
+}
+
 // cls: CLS_P256 .. CLS_P521; wq: a key-table width of the curve; wpb: waves per
 // block, EC_SCALAR_WPB (4) or 1 (the curve's narrowest width only); B: tokens
 // per thread, 1..16.  The launch covers [begin, end) of npad padded slots, all

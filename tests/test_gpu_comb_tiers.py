@@ -28,6 +28,15 @@ from tests import gpu_helpers as H
 pytestmark = pytest.mark.gpu
 
 TAB = {"P-256": "p256", "P-384": "p384", "P-521": "p521"}
+# jobs of the tiled launches below; test_gpu_point_form.py asserts the kernel
+# forms these sizes select
+MID_LAUNCH_JOBS = [40000, 140000]
+ED_LARGE_LAUNCH_JOBS = [20000, 140000]
+
+
+def _tiled(tokens, n):
+    """the tokens repeated to just over n jobs"""
+    return tokens * (n // len(tokens) + 1)
 
 
 def fixtures():
@@ -74,7 +83,7 @@ def test_ecdsa_comb_tier(crv, wq):
         ctx.close()
 
 
-@pytest.mark.parametrize("n", [40000, 140000])
+@pytest.mark.parametrize("n", MID_LAUNCH_JOBS)
 @pytest.mark.parametrize("crv,wq", _ec_tiers())
 def test_ecdsa_comb_tier_mid_launch(crv, wq, n):
     """The same tokens tiled to ~40 k and ~140 k jobs, so the class launch is
@@ -87,8 +96,7 @@ def test_ecdsa_comb_tier_mid_launch(crv, wq, n):
     from cap_amd import _lib
     s = next(x for x in fixtures()["ec"] if x["crv"] == crv and x["wq"] == wq)
     keys = s["keys"]
-    reps = n // len(s["tokens"]) + 1
-    toks = s["tokens"] * reps
+    toks = _tiled(s["tokens"], n)
     assert len(toks) > 16384 * 2
     kid_index = {k["kid"]: i for i, k in enumerate(keys)}
     ctx = _lib.Context()
@@ -228,7 +236,7 @@ def test_ed25519_w16_launch_with_two_tokens_per_thread():
     _resident_two_per_thread(s["keys"], toks, "ed25519", 16)
 
 
-@pytest.mark.parametrize("n", [20000, 140000])
+@pytest.mark.parametrize("n", ED_LARGE_LAUNCH_JOBS)
 @pytest.mark.parametrize("wa", [24, 20, 16])
 def test_ed25519_comb_tier_large_launch(wa, n):
     """The tier's edge tokens tiled past 16 k jobs, so the class launch runs
@@ -238,8 +246,7 @@ def test_ed25519_comb_tier_large_launch(wa, n):
     import bench
     from cap_amd import _lib
     s = fixtures()["ed25519"]
-    reps = n // len(s["tokens"]) + 1
-    toks = s["tokens"] * reps
+    toks = _tiled(s["tokens"], n)
     assert len(toks) > 16384
     kid_index = {k["kid"]: i for i, k in enumerate(s["keys"])}
     ctx = _lib.Context()
