@@ -24,7 +24,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_submit", "jg_wait", "jg_set_chunk", "jg_set_zero_copy", "jg_set_table_budget", "jg_keys_wait_tables",
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
-           "jg_debug_small_path", "jg_claims_scan"]
+           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract"]
 
 
 class JgKey(ctypes.Structure):
@@ -71,6 +71,21 @@ class JgExpect(ctypes.Structure):
 
 assert ctypes.sizeof(JgCJob) == 16
 
+
+class JgClaims(ctypes.Structure):
+    """jg_claims: the registered claims jg_claims_extract read from one payload"""
+    _fields_ = [("exp", ctypes.c_int64), ("nbf", ctypes.c_int64), ("iat", ctypes.c_int64),
+                ("iss_off", ctypes.c_uint32), ("iss_len", ctypes.c_uint32),
+                ("sub_off", ctypes.c_uint32), ("sub_len", ctypes.c_uint32),
+                ("jti_off", ctypes.c_uint32), ("jti_len", ctypes.c_uint32),
+                ("aud_off", ctypes.c_uint32), ("aud_len", ctypes.c_uint32),
+                ("aud_n", ctypes.c_uint32), ("present", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(JgClaims) == 64
+# bit f of jg_claims.present (F_ISS .. F_IAT of kernels/claims.hpp)
+F_ISS, F_SUB, F_JTI, F_AUD, F_EXP, F_NBF, F_IAT = range(1, 8)
+
 _lib = None
 
 
@@ -111,6 +126,7 @@ def lib():
         L.jg_set_table_budget.argtypes = [vp, ctypes.c_uint64]
         L.jg_hash_batch.argtypes = [vp, vp, sz, vp, sz, vp]
         L.jg_claims_scan.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect), vp]
+        L.jg_claims_extract.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect), vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -316,6 +332,37 @@ class Context:
         if rc != 0:
             raise JgError(f"jg_claims_scan rc={rc}: {self.error()}")
         return out.raw[:n]
+
+    def claims_extract(self, arena_bytes, spans, expect, flags=0):
+        """jg_claims_extract: claims_scan's codes and, per span, the jg_claims
+        record of the registered claims -> (codes: bytes, vals: JgClaims array).
+        Both outputs are poisoned with 0xee before the call."""
+        n = len(spans)
+        jobs = (JgCJob * max(1, n))()
+        for i, (off, ln) in enumerate(spans):
+            jobs[i].off, jobs[i].len, jobs[i].flags = off, ln, flags
+        auds = [bytes(a) for a in expect.get("audiences", [])]
+        strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
+        blob = b"".join(strs + auds)
+        e = JgExpect()
+        keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+        e.strs = ctypes.cast(keep, ctypes.c_void_p)
+        e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
+        e.naud = len(auds)
+        for k, a in enumerate(auds[:MAX_AUD]):
+            e.aud_len[k] = len(a)
+        e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
+        e.skew_ns = int(expect["skew_ns"])
+        e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
+        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
+        vals = (JgClaims * max(1, n))()
+        ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
+        buf = bytes(arena_bytes) or b"\0"
+        rc = lib().jg_claims_extract(self.h, buf, len(arena_bytes), jobs, n, ctypes.byref(e), out,
+                                     ctypes.cast(vals, ctypes.c_void_p))
+        if rc != 0:
+            raise JgError(f"jg_claims_extract rc={rc}: {self.error()}")
+        return out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n])
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

@@ -23,6 +23,7 @@
 #include <sys/resource.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <climits>
@@ -1725,6 +1726,11 @@ Result validate_claims(const json::Value& all_claims, const TokenInfo& info, con
 
 Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
                        int64_t now_unix_ns) {
+  return validate_claims(all_claims, info, expected, now_unix_ns, nullptr);
+}
+
+Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
+                       int64_t now_unix_ns, RegisteredClaims* decoded) {
   Result r;
   r.err = alg_header_error(info, expected);
   if (!r.err.empty()) return r;
@@ -1783,6 +1789,18 @@ Result validate_claims(const json::Value& all_claims, const TokenView& info, con
       *has = true;
       *dst = go_f64_to_i64(v.num);                                 // NumericDate(f)
     }
+  }
+  if (decoded) {
+    decoded->Issuer = std::string(iss);
+    decoded->Subject = std::string(sub);
+    decoded->ID = std::string(jti);
+    decoded->Audience.clear();
+    if (aud && aud->kind == json::Value::String) decoded->Audience.emplace_back(aud->str.view());
+    else if (aud)
+      for (const auto& a : aud->arr) decoded->Audience.emplace_back(a.str.view());
+    decoded->Expiry = has_exp ? std::optional<int64_t>(exp) : std::nullopt;
+    decoded->NotBefore = has_nbf ? std::optional<int64_t>(nbf) : std::nullopt;
+    decoded->IssuedAt = has_iat ? std::optional<int64_t>(iat) : std::nullopt;
   }
   // time defaulting (jwt/jwt.go:117-170)  [R38]
   if (!has_iat) iat = 0;
@@ -1881,11 +1899,93 @@ const char* claim_code_error(uint8_t code) {
 }  // namespace
 
 namespace {
-// CheckBatch's flow; put(i, ok, err) receives token i's outcome once, from a
-// host thread (CheckBatch keeps the strings, CheckVerdicts only the bit)
-template <class Put>
+// Appends bytes [off, off + len) of the payload that `seg` (canonical unpadded
+// base64url: the scan decided it) encodes, decoding only the characters that
+// carry them: [4 (off / 3), 4 ceil((off + len) / 3)).
+void append_span(std::string& out, std::string_view seg, uint32_t off, uint32_t len) {
+  // kTrip[k][c]: the sextet of character c, shifted to its place in a group's 24 bits
+  struct Tables {
+    uint32_t t[4][256];
+  };
+  static const Tables kTrip = [] {
+    Tables T{};
+    const char* abc = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
+    for (int k = 0; k < 4; ++k)
+      for (uint32_t v = 0; v < 64; ++v) T.t[k][(uint8_t)abc[v]] = v << (18 - 6 * k);
+    return T;
+  }();
+  if (len == 0) return;
+  const size_t g0 = off / 3, g1 = ((size_t)off + len + 2) / 3;     // groups of 4 characters -> 3 bytes
+  const size_t skip = off - 3 * g0, base = out.size();
+  out.resize(base + 3 * (g1 - g0));
+  char* w = &out[base];
+  const uint8_t* p = (const uint8_t*)seg.data();
+  const size_t whole = std::min(g1, seg.size() / 4);               // groups with all four characters
+  size_t g = g0;
+  for (; g < whole; ++g, w += 3) {
+    const uint32_t trip = kTrip.t[0][p[4 * g]] | kTrip.t[1][p[4 * g + 1]] | kTrip.t[2][p[4 * g + 2]] | kTrip.t[3][p[4 * g + 3]];
+    w[0] = (char)(trip >> 16);
+    w[1] = (char)(trip >> 8);
+    w[2] = (char)trip;
+  }
+  for (; g < g1; ++g, w += 3) {                                    // the segment's last, short group
+    uint32_t trip = 0;
+    for (size_t k = 0; k < 4 && 4 * g + k < seg.size(); ++k) trip |= kTrip.t[k][p[4 * g + k]];
+    w[0] = (char)(trip >> 16);
+    w[1] = (char)(trip >> 8);
+    w[2] = (char)trip;
+  }
+  if (skip) std::memmove(&out[base], &out[base + skip], len);
+  out.resize(base + len);
+}
+
+// The elements of an aud value's text, "s" or [ "a", "b" ]: no escapes (the
+// scan decided it), so they are the quoted runs.  each(begin, length)
+template <class F>
+void aud_elements(std::string_view text, F&& each) {
+  for (size_t q = text.find('"'); q != std::string_view::npos; q = text.find('"', q + 1)) {
+    const size_t e = text.find('"', q + 1);
+    if (e == std::string_view::npos) break;
+    each(q + 1, e - q - 1);
+    q = e;
+  }
+}
+
+// jwt.Claims from the scan's record of a payload it decided
+RegisteredClaims claims_of_record(std::string_view seg, const jg_claims& v) {
+  RegisteredClaims c;
+  append_span(c.Issuer, seg, v.iss_off, v.iss_len);
+  append_span(c.Subject, seg, v.sub_off, v.sub_len);
+  append_span(c.ID, seg, v.jti_off, v.jti_len);
+  if (v.aud_n) {
+    std::string text;
+    append_span(text, seg, v.aud_off, v.aud_len);
+    c.Audience.reserve(v.aud_n);
+    aud_elements(text, [&](size_t at, size_t n) { c.Audience.emplace_back(text, at, n); });
+  }
+  if ((v.present >> 5) & 1u) c.Expiry = v.exp;
+  if ((v.present >> 6) & 1u) c.NotBefore = v.nbf;
+  if ((v.present >> 7) & 1u) c.IssuedAt = v.iat;
+  return c;
+}
+
+// CheckBatch's flow.  X = false: put(i, ok, err) receives token i's outcome
+// once, from a host thread (CheckBatch keeps the strings, CheckVerdicts only
+// the bit).  X = true (RegisteredBatch): the scan is jg_claims_extract, its
+// records lie behind the jobs in the same pinned block, and `put` is a sink
+// that receives each token once: reject(chunk, i, err); record(chunk, i,
+// payload segment, jg_claims) for a token the device accepted;
+// claims(chunk, i, jwt.Claims) for one the host path accepted.  chunk: which of
+// make_chunks(n, host_threads())'s ranges i lies in; one thread per chunk, in
+// index order.
+template <bool X, class Put>
 void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected& expected, CheckStats* stats,
                 Put&& put) {
+  // a token that is not accepted carries no claims
+  auto reject = [&](size_t c, size_t i, std::string&& err) {
+    if constexpr (X) put.reject(c, i, std::move(err));
+    else put(i, false, std::move(err));
+  };
   const int64_t now = expected.has_now ? expected.now_unix_ns : wall_now_ns();
   const size_t n = tokens.size();
   const int th = host_threads();
@@ -1924,9 +2024,11 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   // Both arrays live in one pinned block of the engine's pool (DMA at link
   // speed, no page faults in steady state).
   Engine& eng = ks_->engine();
-  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + 16);
+  const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | codes
+  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + rec_bytes + 16);
   jg_cjob* const jobs = (jg_cjob*)scanbuf.get();
-  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob);
+  jg_claims* const recs = (jg_claims*)(scanbuf.get() + n * sizeof(jg_cjob));
+  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes;
   std::memset(code, JG_CL_HOST, n);
   bool have_jobs = false;
   bool scan_failed = false;
@@ -1953,7 +2055,8 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     });
     pt.lap("scan-jobs");
     try {
-      eng.claims_scan(V.arena, V.arena_len, jobs, n, &ex, code, true);
+      if constexpr (X) eng.claims_extract(V.arena, V.arena_len, jobs, n, &ex, code, recs, true);
+      else eng.claims_scan(V.arena, V.arena_len, jobs, n, &ex, code, true);
     } catch (const DeviceError& e) {
       // as a failed verify: the tokens the scan carried get its error (no
       // host fallback for them) and the context is recreated after the batch
@@ -1975,11 +2078,11 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
       if (!(t.parsed && !V->failed[i] && V->any[i])) {
         Result r;                                     // the key set's own error string; no claims are read
         ks_->finish(*V, i, r);
-        put(i, false, "error verifying token signature: " + r.err);
+        reject(c, i, "error verifying token signature: " + r.err);
         continue;
       }
       if (scan_failed && have_jobs && jobs[i].len) {
-        put(i, false, std::string(scan_err));
+        reject(c, i, std::string(scan_err));
         continue;
       }
       if (code[i] == JG_CL_HOST) {
@@ -1987,20 +2090,34 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
         Result r;
         ks_->finish(*V, i, r);
         if (!r.ok) {
-          put(i, false, "error verifying token signature: " + r.err);
+          reject(c, i, "error verifying token signature: " + r.err);
           continue;
         }
-        Result v = validate_claims(r.claims, t.view(), expected, now);
-        put(i, v.ok, std::move(v.err));
+        if constexpr (X) {
+          RegisteredClaims rc;
+          Result v = validate_claims(r.claims, t.view(), expected, now, &rc);
+          if (v.ok) put.claims(c, i, std::move(rc));
+          else reject(c, i, std::move(v.err));
+        } else {
+          Result v = validate_claims(r.claims, t.view(), expected, now);
+          put(i, v.ok, std::move(v.err));
+        }
         continue;
       }
       ++ns;
       std::string err = alg_header_error(t.view(), expected);
       if (!err.empty()) {
-        put(i, false, std::move(err));
+        reject(c, i, std::move(err));
         continue;
       }
-      put(i, code[i] == JG_CL_OK, std::string(claim_code_error(code[i])));
+      if constexpr (X) {
+        // the payload segment ends the signing input; its length is the job's
+        if (code[i] != JG_CL_OK) reject(c, i, std::string(claim_code_error(code[i])));
+        else
+          put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i]);
+      } else {
+        put(i, code[i] == JG_CL_OK, std::string(claim_code_error(code[i])));
+      }
     }
     n_scan[c] = ns;
     n_host[c] = nh;
@@ -2021,17 +2138,148 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
 std::vector<CheckResult> Validator::CheckBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
                                                CheckStats* stats) {
   std::vector<CheckResult> out(tokens.size());
-  check_core(ks_, tokens, expected, stats, [&](size_t i, bool ok, std::string&& err) {
+  check_core<false>(ks_, tokens, expected, stats, [&](size_t i, bool ok, std::string&& err) {
     out[i].ok = ok;
     out[i].err = std::move(err);
   });
   return out;
 }
 
+namespace {
+struct RowSink {                                   // RegisteredBatch: one RegisteredResult per token
+  std::vector<RegisteredResult>& out;
+  void reject(size_t, size_t i, std::string&& err) { out[i].err = std::move(err); }
+  void record(size_t, size_t i, std::string_view seg, const jg_claims& v) {
+    out[i].ok = true;
+    out[i].claims = claims_of_record(seg, v);
+  }
+  void claims(size_t, size_t i, RegisteredClaims&& c) {
+    out[i].ok = true;
+    out[i].claims = std::move(c);
+  }
+};
+
+// RegisteredCols: the fixed columns are written in place; each merge thread
+// appends its chunk's bytes to a part of its own, with offsets relative to the
+// part, and finish() moves the parts into the caller's memory
+struct ColumnSink {
+  struct Part {
+    std::string str[3], aud;
+    std::vector<uint32_t> aud_end;                 // each element's end in `aud`
+    bool sized = false;
+  };
+  const RegisteredColumns& R;
+  const Chunks& ch;
+  std::vector<Part> parts;
+  uint32_t* off[3];
+  ColumnSink(const RegisteredColumns& r, const Chunks& chunks)
+      : R(r), ch(chunks), parts(chunks.count()), off{r.iss_off, r.sub_off, r.jti_off} {}
+  // The tokens of one batch mostly have one shape: the chunk's first record
+  // sizes the part (a quarter over), so that it does not grow a dozen times
+  // into fresh pages while 16 threads do the same.
+  void size_part(Part& P, size_t c, const jg_claims& v) {
+    P.sized = true;
+    const size_t cnt = ch.b[c + 1] - ch.b[c];
+    auto room = [&](uint32_t len) { return cnt * ((size_t)len + len / 4 + 4); };
+    P.str[0].reserve(room(v.iss_len));
+    P.str[1].reserve(room(v.sub_len));
+    P.str[2].reserve(room(v.jti_len));
+    P.aud.reserve(room(v.aud_len));
+    P.aud_end.reserve(cnt * ((size_t)v.aud_n + 1));
+  }
+  void row(Part& P, size_t i, bool ok, uint32_t present, int64_t exp, int64_t nbf, int64_t iat) {
+    R.ok[i] = ok ? 1 : 0;
+    R.present[i] = (uint8_t)(present & 0xe0u);
+    R.exp[i] = exp;
+    R.nbf[i] = nbf;
+    R.iat[i] = iat;
+    for (int k = 0; k < 3; ++k) off[k][i + 1] = (uint32_t)P.str[k].size();
+    R.aud_tok[i + 1] = (uint32_t)P.aud_end.size();
+  }
+  void reject(size_t c, size_t i, std::string&&) { row(parts[c], i, false, 0, 0, 0, 0); }
+  void record(size_t c, size_t i, std::string_view seg, const jg_claims& v) {
+    Part& P = parts[c];
+    if (!P.sized) size_part(P, c, v);
+    append_span(P.str[0], seg, v.iss_off, v.iss_len);
+    append_span(P.str[1], seg, v.sub_off, v.sub_len);
+    append_span(P.str[2], seg, v.jti_off, v.jti_len);
+    if (v.aud_n) {
+      // the value's text goes to the end of the part, its elements are moved down over it
+      const size_t at = P.aud.size();
+      append_span(P.aud, seg, v.aud_off, v.aud_len);
+      size_t w = at;
+      aud_elements(std::string_view(P.aud).substr(at), [&](size_t b, size_t n) {
+        std::memmove(&P.aud[w], &P.aud[at + b], n);
+        w += n;
+        P.aud_end.push_back((uint32_t)w);
+      });
+      P.aud.resize(w);
+    }
+    row(P, i, true, v.present, v.exp, v.nbf, v.iat);
+  }
+  void claims(size_t c, size_t i, RegisteredClaims&& cl) {
+    Part& P = parts[c];
+    P.str[0] += cl.Issuer;
+    P.str[1] += cl.Subject;
+    P.str[2] += cl.ID;
+    for (const auto& a : cl.Audience) {
+      P.aud += a;
+      P.aud_end.push_back((uint32_t)P.aud.size());
+    }
+    row(P, i, true, (cl.Expiry ? 1u << 5 : 0u) | (cl.NotBefore ? 1u << 6 : 0u) | (cl.IssuedAt ? 1u << 7 : 0u),
+        cl.Expiry.value_or(0), cl.NotBefore.value_or(0), cl.IssuedAt.value_or(0));
+  }
+  void finish() {
+    const size_t nc = parts.size();
+    std::vector<size_t> base[4], ebase(nc + 1, 0);
+    for (int k = 0; k < 4; ++k) {
+      base[k].assign(nc + 1, 0);
+      for (size_t c = 0; c < nc; ++c) base[k][c + 1] = base[k][c] + (k < 3 ? parts[c].str[k] : parts[c].aud).size();
+    }
+    for (size_t c = 0; c < nc; ++c) ebase[c + 1] = ebase[c] + parts[c].aud_end.size();
+    char* data[4];
+    for (int k = 0; k < 4; ++k) data[k] = (char*)R.alloc((RegisteredColumns::Var)k, base[k][nc]);
+    uint32_t* const aud_off = (uint32_t*)R.alloc(RegisteredColumns::AUD_OFF, 4 * (ebase[nc] + 1));
+    aud_off[0] = 0;
+    for (int k = 0; k < 3; ++k) off[k][0] = 0;
+    R.aud_tok[0] = 0;
+    run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
+      const Part& P = parts[c];
+      for (int k = 0; k < 4; ++k) {
+        const std::string& src = k < 3 ? P.str[k] : P.aud;
+        if (!src.empty()) std::memcpy(data[k] + base[k][c], src.data(), src.size());
+      }
+      for (size_t i = lo; i < hi; ++i) {
+        for (int k = 0; k < 3; ++k) off[k][i + 1] += (uint32_t)base[k][c];
+        R.aud_tok[i + 1] += (uint32_t)ebase[c];
+      }
+      for (size_t j = 0; j < P.aud_end.size(); ++j) aud_off[ebase[c] + j + 1] = (uint32_t)(base[3][c] + P.aud_end[j]);
+    });
+  }
+};
+}  // namespace
+
+std::vector<RegisteredResult> Validator::RegisteredBatch(const std::vector<std::string_view>& tokens,
+                                                         const Expected& expected, CheckStats* stats) {
+  std::vector<RegisteredResult> out(tokens.size());
+  check_core<true>(ks_, tokens, expected, stats, RowSink{out});
+  return out;
+}
+
+void Validator::RegisteredCols(const std::vector<std::string_view>& tokens, const Expected& expected,
+                               const RegisteredColumns& out, CheckStats* stats) {
+  const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
+  ColumnSink sink(out, ch);
+  check_core<true>(ks_, tokens, expected, stats, sink);
+  PhaseTimer pt("check");
+  sink.finish();
+  pt.lap("columns");
+}
+
 std::vector<uint8_t> Validator::CheckVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
                                               CheckStats* stats) {
   std::vector<uint8_t> ok(tokens.size(), 0);
-  check_core(ks_, tokens, expected, stats, [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
+  check_core<false>(ks_, tokens, expected, stats, [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
   return ok;
 }
 
@@ -2061,6 +2309,23 @@ void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* job
   if (rc == -1)
     throw std::logic_error(std::string("capjwt: jg_claims_scan rejected the host's jobs: ") + jg_last_error(ctx_));
   if (rc != 0) fail_device(std::string("capjwt: jg_claims_scan: ") + jg_last_error(ctx_));
+}
+
+// ... and so is jg_claims_extract (RegisteredBatch), for the same providers
+extern "C" __attribute__((weak)) int jg_claims_extract(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
+                                                       const jg_expect*, uint8_t*, jg_claims*);
+
+void Engine::claims_extract(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
+                            uint8_t* codes, void* vals, bool inside_verify) {
+  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
+  if (!inside_verify) life.lock();
+  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
+  if (!jg_claims_extract) fail_device("capjwt: jg_claims_extract: not provided by the loaded verifier library");
+  const int rc = jg_claims_extract(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect, codes,
+                                   (jg_claims*)vals);
+  if (rc == -1)
+    throw std::logic_error(std::string("capjwt: jg_claims_extract rejected the host's jobs: ") + jg_last_error(ctx_));
+  if (rc != 0) fail_device(std::string("capjwt: jg_claims_extract: ") + jg_last_error(ctx_));
 }
 
 namespace {

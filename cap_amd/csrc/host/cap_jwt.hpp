@@ -16,6 +16,8 @@
 //   NewValidator / Validate   jwt/jwt.go:25-202       NewValidator / Validator::Validate
 //   (north star) ValidateBatch                        Validator::ValidateBatch
 //   (verdict only) CheckBatch                         Validator::CheckBatch (claims scanned on the GPU)
+//   jwt.Claims after Validate jwt/jwt.go:107-116      Validator::RegisteredBatch (verdict + registered claims
+//                                                     from the GPU scan, no claims map)
 //   SupportedSigningAlgorithm jwt/algs.go:38-46       SupportedSigningAlgorithm
 //
 // There is no CPU verification path: a KeySet whose GPU context cannot be
@@ -30,6 +32,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <shared_mutex>
 #include <stdexcept>
 #include <string>
@@ -193,6 +196,9 @@ class Engine {
   // (that call already holds the context's lifetime lock).
   void claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
                    uint8_t* codes, bool inside_verify = false);
+  // ... and vals[i] = the jg_claims record of job i (jg_claims_extract)
+  void claims_extract(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
+                      uint8_t* codes, void* vals, bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -422,6 +428,38 @@ struct CheckStats {
   size_t scanned = 0, host = 0;
 };
 
+// go-jose's jwt.Claims after json.Unmarshal (jwt/jwt.go:107-116): what Validate
+// itself decodes from the claims map to run its checks
+struct RegisteredClaims {
+  std::string Issuer, Subject, ID;
+  std::vector<std::string> Audience;
+  std::optional<int64_t> Expiry, NotBefore, IssuedAt;   // nil for absent or null
+};
+// Validate's (ok, error string) and, when ok, the registered claims
+struct RegisteredResult {
+  bool ok = false;
+  std::string err;
+  RegisteredClaims claims;
+};
+// RegisteredBatch as columns (RegisteredBlob), written straight into memory the
+// caller supplies; no per-token object is built for a token the device decides.
+// Rows of a rejected token are empty (zero, and equal offsets).
+struct RegisteredColumns {
+  // one entry per token
+  uint8_t* ok = nullptr;          // 1 = Validate returns no error
+  uint8_t* present = nullptr;     // bit 5 exp, 6 nbf, 7 iat: the date is there (not absent, not null)
+  int64_t *exp = nullptr, *nbf = nullptr, *iat = nullptr;
+  // n + 1 offsets each: token i's string is data[off[i], off[i + 1]); token i's
+  // audiences are elements [aud_tok[i], aud_tok[i + 1])
+  uint32_t *iss_off = nullptr, *sub_off = nullptr, *jti_off = nullptr, *aud_tok = nullptr;
+  // The columns whose size the call finds out: the bytes of iss / sub / jti,
+  // of the audience elements back to back, and the elements' offsets (uint32,
+  // one more than there are elements).  alloc(which, bytes) is called once for
+  // each, from the calling thread, and returns where to write them.
+  enum Var { ISS = 0, SUB = 1, JTI = 2, AUD = 3, AUD_OFF = 4 };
+  std::function<void*(Var which, size_t bytes)> alloc;
+};
+
 class Validator {
  public:
   explicit Validator(KeySet* ks) : ks_(ks) {}
@@ -440,6 +478,19 @@ class Validator {
   // string outlives the call (CheckBlob)
   std::vector<uint8_t> CheckVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
                                      CheckStats* stats = nullptr);
+  // CheckBatch plus what nearly every caller reads after a successful Validate:
+  // ok / err are CheckBatch's, token for token, and an accepted token carries its
+  // jwt.Claims.  The scan returns the values with the verdict
+  // (jg_claims_extract): the dates as numbers, the strings as spans of the
+  // decoded payload that a few bytes of base64 decoding turn into the value --
+  // no JSON parse, no claims map.  A token the scan leaves to the host takes
+  // the struct validate_claims decodes.
+  std::vector<RegisteredResult> RegisteredBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                                CheckStats* stats = nullptr);
+  // RegisteredBatch's accept bits and claims as columns, built by the host
+  // threads that merge the scan's records (RegisteredBlob)
+  void RegisteredCols(const std::vector<std::string_view>& tokens, const Expected& expected,
+                      const RegisteredColumns& out, CheckStats* stats = nullptr);
  private:
   KeySet* ks_;
 };
@@ -452,6 +503,10 @@ Result validate_claims(const json::Value& all_claims, const TokenInfo& info, con
                        int64_t now_unix_ns);
 Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
                        int64_t now_unix_ns);
+// ... and *decoded = the jwt.Claims struct the checks ran on (set once the
+// claims map unmarshals, whatever the checks then say)
+Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
+                       int64_t now_unix_ns, RegisteredClaims* decoded);
 // Expected's three leeways after Go's defaulting (jwt/jwt.go:128-170): the
 // clock skew in ns (negative -> 0, 0 -> one minute) and the leeways that
 // default a missing exp / nbf, as the whole seconds Go adds (negative -> 0,

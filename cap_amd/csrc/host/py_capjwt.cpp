@@ -481,6 +481,101 @@ PYBIND11_MODULE(_capjwt_host, m) {
         }
         return py::make_tuple(py::bytes(ok), st.scanned, st.host);
       })
+      .def("registered_batch", [](PyValidator& s, py::sequence toks, const Expected& e) {
+        // check_batch with jwt.Claims: ([(claims dict or None, error or None)], scanned, host)
+        auto v = as_strings(toks);
+        std::vector<RegisteredResult> rs;
+        CheckStats st;
+        {
+          py::gil_scoped_release rel;
+          rs = s.v->RegisteredBatch(views(v), e, &st);
+        }
+        auto date = [](const std::optional<int64_t>& d) -> py::object {
+          return d ? py::object(py::int_(*d)) : py::object(py::none());
+        };
+        py::list out(rs.size());
+        for (size_t i = 0; i < rs.size(); ++i) {
+          if (!rs[i].ok) {
+            out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
+            continue;
+          }
+          const RegisteredClaims& c = rs[i].claims;
+          py::dict d;
+          d["iss"] = py::str(c.Issuer);
+          d["sub"] = py::str(c.Subject);
+          d["jti"] = py::str(c.ID);
+          py::list aud;
+          for (const auto& a : c.Audience) aud.append(py::str(a));
+          d["aud"] = aud;
+          d["exp"] = date(c.Expiry);
+          d["nbf"] = date(c.NotBefore);
+          d["iat"] = date(c.IssuedAt);
+          out[i] = py::make_tuple(d, py::none());
+        }
+        return py::make_tuple(out, st.scanned, st.host);
+      })
+      .def("registered_blob", [](PyValidator& s, py::bytes blob, const Expected& e) {
+        // check_blob with the registered claims as columns: newline-separated
+        // tokens in, (dict of bytes, scanned, host) out -- no per-token object
+        char* bp = nullptr;
+        Py_ssize_t bn = 0;
+        if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+        // the columns are bytes objects from the start: the host threads write
+        // into them, nothing is copied afterwards
+        auto fresh = [](size_t bytes) {
+          PyObject* o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)bytes);
+          if (!o) throw py::error_already_set();
+          return py::reinterpret_steal<py::bytes>(o);
+        };
+        auto mem = [](py::bytes& b) { return (void*)PyBytes_AS_STRING(b.ptr()); };
+        const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](const char* what) {
+          if (!trace) return;
+          const auto t1 = std::chrono::steady_clock::now();
+          std::fprintf(stderr, "[capjwt] rblob %-12s %8.2f ms\n", what,
+                       std::chrono::duration<double, std::milli>(t1 - t0).count());
+          t0 = t1;
+        };
+        auto toks = split_lines(bp, (size_t)bn);
+        lap("split");
+        const size_t n = toks.size();
+        py::bytes ok = fresh(n), present = fresh(n), exp = fresh(8 * n), nbf = fresh(8 * n), iat = fresh(8 * n);
+        py::bytes off[4] = {fresh(4 * (n + 1)), fresh(4 * (n + 1)), fresh(4 * (n + 1)), fresh(4 * (n + 1))};
+        py::bytes var[5];
+        RegisteredColumns R;
+        R.ok = (uint8_t*)mem(ok);
+        R.present = (uint8_t*)mem(present);
+        R.exp = (int64_t*)mem(exp);
+        R.nbf = (int64_t*)mem(nbf);
+        R.iat = (int64_t*)mem(iat);
+        R.iss_off = (uint32_t*)mem(off[0]);
+        R.sub_off = (uint32_t*)mem(off[1]);
+        R.jti_off = (uint32_t*)mem(off[2]);
+        R.aud_tok = (uint32_t*)mem(off[3]);
+        R.alloc = [&](RegisteredColumns::Var which, size_t bytes) {
+          py::gil_scoped_acquire gil;
+          var[which] = fresh(bytes);
+          return mem(var[which]);
+        };
+        CheckStats st;
+        {
+          py::gil_scoped_release rel;
+          s.v->RegisteredCols(toks, e, R, &st);
+        }
+        lap("registered");
+        py::dict d;
+        d["ok"] = ok;
+        d["present"] = present;
+        d["exp"] = exp;
+        d["nbf"] = nbf;
+        d["iat"] = iat;
+        d["iss"] = py::make_tuple(off[0], var[RegisteredColumns::ISS]);
+        d["sub"] = py::make_tuple(off[1], var[RegisteredColumns::SUB]);
+        d["jti"] = py::make_tuple(off[2], var[RegisteredColumns::JTI]);
+        d["aud"] = py::make_tuple(off[3], var[RegisteredColumns::AUD_OFF], var[RegisteredColumns::AUD]);
+        return py::make_tuple(d, st.scanned, st.host);
+      })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {
         // Measurement helper (bench.py `single`): `callers` host threads, each

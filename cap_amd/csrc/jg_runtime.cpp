@@ -715,6 +715,7 @@ struct Device {
   hipStream_t clstream = nullptr;
   std::mutex cl_mu;
   Grow cl_arena, cl_jobs, cl_out, cl_expect;
+  Grow cl_vals;                     // jg_claims_extract's records
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -3434,6 +3435,55 @@ int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     launch_claims_scan(a, j, (int64_t)njobs, e, o, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(e.what());
+    return -2;
+  }
+}
+
+// jg_claims_scan with the records: the same checks, stream, lock and kept
+// buffers, one more device buffer (cl_vals) and one more copy back
+int jg_claims_extract(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                      const jg_cjob* jobs, size_t njobs, const jg_expect* expect,
+                      uint8_t* code_out, jg_claims* vals_out) {
+  if (!ctx || !expect || (njobs > 0 && (!jobs || !code_out || !vals_out)) || (arena_len > 0 && !arena)) return -1;
+  if (njobs == 0) return 0;
+  if (ctx->poisoned.load()) {
+    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
+    return -2;
+  }
+  auto E = std::make_unique<jgclaims::Expect>();
+  if (!jgclaims::resolve(*expect, E.get())) {
+    ctx->set_err("jg_claims_extract: more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9");
+    return -1;
+  }
+  for (size_t i = 0; i < njobs; ++i) {
+    const jg_cjob& J = jobs[i];
+    if (J.flags != 0 || J.off > arena_len || J.len > arena_len - J.off) {
+      ctx->set_err("jg_claims_extract: job " + std::to_string(i) + " has flags set or a span past the arena");
+      return -1;
+    }
+  }
+  try {
+    Device* d = ctx->devs[0].get();
+    std::lock_guard<std::mutex> g(d->cl_mu);
+    HIPCHK(hipSetDevice(d->id));
+    const hipStream_t s = d->clstream;
+    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
+    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
+    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
+    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
+    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
+    jgclaims::Expect* e = (jgclaims::Expect*)d->cl_expect.get(sizeof(jgclaims::Expect));
+    HIPCHK(hipMemcpyAsync(e, E.get(), sizeof(jgclaims::Expect), hipMemcpyHostToDevice, s));
+    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
+    jg_claims* v = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
+    launch_claims_extract(a, j, (int64_t)njobs, e, o, v, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   } catch (const std::exception& e) {

@@ -54,7 +54,45 @@ __global__ void __launch_bounds__(kBlock) k_claims_scan(const uint8_t* __restric
   code_out[i] = claims_decide(src, J.len, E);
 }
 
+// k_claims_scan that also keeps what it read: vals_out[i] is token i's record of
+// registered claims (jg_claims, 64 bytes), written as four 16-byte stores
+__global__ void __launch_bounds__(kBlock) k_claims_extract(const uint8_t* __restrict__ arena,
+                                                           const jg_cjob* __restrict__ jobs, int64_t n,
+                                                           const Expect* __restrict__ expect,
+                                                           uint8_t* __restrict__ code_out,
+                                                           jg_claims* __restrict__ vals_out) {
+  __shared__ Expect E;
+  {
+    const uint32_t* src = (const uint32_t*)expect;
+    uint32_t* dst = (uint32_t*)&E;
+    for (uint32_t k = threadIdx.x; k < sizeof(Expect) / 4; k += kBlock) dst[k] = src[k];
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const jg_cjob J = jobs[i];
+  WordSrc src;
+  src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
+  src.shift8 = 8u * (uint32_t)(J.off & 3);
+  src.cur = src.aligned[0];
+  jg_claims v;                                  // fields only: stays in registers
+  code_out[i] = claims_extract(src, J.len, E, &v);
+  static_assert(sizeof(jg_claims) == 64, "the record is four 16-byte stores");
+  uint4* o = (uint4*)(vals_out + i);
+  o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
+  o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
+  o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
+  o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
+}
+
 }  // namespace
+
+void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
+                           uint8_t* code_out, jg_claims* vals_out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_claims_extract, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs, n,
+                     expect, code_out, vals_out);
+}
 
 void launch_claims_scan(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
                         uint8_t* code_out, hipStream_t s) {

@@ -18,8 +18,14 @@
 // `uint32_t word(uint32_t g)` = characters [4g, 4g+4) little-endian), so the
 // CPU tests compile the very code the kernel runs.  All state is scalar: no
 // arrays indexed at run time, nothing that would go to scratch.
+//
+// claims_extract() is the same scan with extraction switched on at compile
+// time (ScanT<true>): the same code, plus a jg_claims record of the registered
+// claims -- the dates as numbers, iss / sub / jti / aud as byte spans into the
+// decoded payload.  ScanT<false> is the verdict-only scan, unchanged.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "../../../include/jg.h"
 
@@ -95,7 +101,20 @@ JG_CL_HD uint32_t field_of(uint32_t kw) {            // three upper-cased key by
        : kw == 0x455850u ? F_EXP : kw == 0x4e4246u ? F_NBF : kw == 0x494154u ? F_IAT : (uint32_t)F_NONE;
 }
 
-struct Scan {
+// What the extracting form (claims_extract) keeps beside the verdict's state:
+// where the registered strings lie in the decoded payload, and which fields the
+// payload names with a non-null value.  Scalars, latched with selects.
+struct Extract {
+  uint32_t dpos = 0;                // decoded position of the byte step() is reading: 3 g + k
+  uint32_t iss_off = 0, iss_len = 0, sub_off = 0, sub_len = 0, jti_off = 0, jti_len = 0;
+  uint32_t aud_off = 0, aud_len = 0, aud_n = 0;
+  uint32_t present = 0;
+};
+struct NoExtract {};
+
+// X: also record the claim values (Extract); X = false is the verdict-only scan
+template <bool X>
+struct ScanT : std::conditional_t<X, Extract, NoExtract> {
   uint32_t st = ST_START;
   uint32_t depth = 0, stk = 0;      // open containers; bit d: container d+1 is an object
   uint32_t field = F_NONE;          // the top-level member whose value comes next
@@ -111,27 +130,33 @@ struct Scan {
   uint32_t aud_found = 0;
   int64_t exp = 0, nbf = 0, iat = 0;
 };
+using Scan = ScanT<false>;
 
 JG_CL_HD bool is_ws(uint32_t c) { return c == 0x20u || c == 0x09u || c == 0x0au || c == 0x0du; }
 JG_CL_HD bool is_digit(uint32_t c) { return c - 0x30u < 10u; }
 
-JG_CL_HD void end_value(Scan& s) { s.st = s.depth == 0 ? (uint32_t)ST_DONE : (uint32_t)ST_AFTER; }
+template <bool X>
+JG_CL_HD void end_value(ScanT<X>& s) { s.st = s.depth == 0 ? (uint32_t)ST_DONE : (uint32_t)ST_AFTER; }
 
-JG_CL_HD void push(Scan& s, uint32_t is_obj) {
+template <bool X>
+JG_CL_HD void push(ScanT<X>& s, uint32_t is_obj) {
   if (s.depth >= 32u) { s.bad = 1; return; }
   s.stk = (s.stk & ~(1u << s.depth)) | (is_obj << s.depth);
   ++s.depth;
 }
 
-JG_CL_HD void pop(Scan& s, uint32_t is_obj) {
+template <bool X>
+JG_CL_HD void pop(ScanT<X>& s, uint32_t is_obj) {
   if (((s.stk >> (s.depth - 1u)) & 1u) != is_obj) { s.bad = 1; return; }
   --s.depth;
+  if constexpr (X) s.aud_len = s.depth == 1u && s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud's ]
   if (s.depth == 1u) s.aud_arr = 0;
   end_value(s);
 }
 
 // the first byte of a value
-JG_CL_HD void begin_value(Scan& s, uint32_t c, const Expect& E) {
+template <bool X>
+JG_CL_HD void begin_value(ScanT<X>& s, uint32_t c, const Expect& E) {
   const uint32_t f = s.depth == 1u ? s.field : (uint32_t)F_NONE;
   const uint32_t elem = s.depth == 2u && s.aud_arr;        // an element of aud's array
   const uint32_t is_str3 = f - F_ISS < 3u, is_date = f - F_EXP < 3u;
@@ -144,10 +169,24 @@ JG_CL_HD void begin_value(Scan& s, uint32_t c, const Expect& E) {
     s.cmpf = elem ? (uint32_t)F_AUD : f;
     s.cand = is_str3 ? (E.len[f - 1u] ? 1u << (f - 1u) : 0u)
            : (f == F_AUD || elem) ? ((1u << E.naud) - 1u) << 3 : 0u;
+    if constexpr (X) {
+      const uint32_t in = s.dpos + 1u;                 // the first byte between the quotes
+      s.iss_off = f == F_ISS ? in : s.iss_off;
+      s.sub_off = f == F_SUB ? in : s.sub_off;
+      s.jti_off = f == F_JTI ? in : s.jti_off;
+      s.aud_off = f == F_AUD ? s.dpos : s.aud_off;
+      s.aud_n = f == F_AUD ? 1u : s.aud_n + elem;
+      s.present |= (is_str3 || f == F_AUD) ? 1u << f : 0u;
+    }
   } else if (c == '{' || c == '[') {
     const uint32_t arr = c == '[';
-    if (arr && f == F_AUD) s.aud_arr = 1;
-    else if (f != F_NONE || elem) s.bad = 1;
+    if (arr && f == F_AUD) {
+      s.aud_arr = 1;
+      if constexpr (X) {
+        s.aud_off = s.dpos;
+        s.present |= 1u << F_AUD;
+      }
+    } else if (f != F_NONE || elem) s.bad = 1;
     push(s, arr ^ 1u);
     s.st = arr ? (uint32_t)ST_ARR_FIRST : (uint32_t)ST_OBJ_FIRST;
   } else if (c == 't' || c == 'f' || c == 'n') {
@@ -169,7 +208,8 @@ JG_CL_HD void begin_value(Scan& s, uint32_t c, const Expect& E) {
 }
 
 // a number ended in front of the current byte
-JG_CL_HD void end_number(Scan& s) {
+template <bool X>
+JG_CL_HD void end_number(ScanT<X>& s) {
   if (s.isdate) {
     // -?(0|[1-9][0-9]{0,14}), not -0: exact in float64 and far from any wrap
     if (s.st != ST_NUM_ZERO && s.st != ST_NUM_INT) s.bad = 1;
@@ -179,11 +219,13 @@ JG_CL_HD void end_number(Scan& s) {
     s.exp = s.field == F_EXP ? v : s.exp;
     s.nbf = s.field == F_NBF ? v : s.nbf;
     s.iat = s.field == F_IAT ? v : s.iat;
+    if constexpr (X) s.present |= 1u << s.field;
   }
   s.st = ST_AFTER;
 }
 
-JG_CL_HD void step(Scan& s, uint32_t c, const Expect& E) {
+template <bool X>
+JG_CL_HD void step(ScanT<X>& s, uint32_t c, const Expect& E) {
   if (s.st >= ST_NUM_MINUS && s.st <= ST_NUM_FRAC) {
     const uint32_t d = is_digit(c);
     uint32_t nx = ST_AFTER;                           // ST_AFTER: the number ends here
@@ -225,6 +267,12 @@ JG_CL_HD void step(Scan& s, uint32_t c, const Expect& E) {
           }
           if (s.cmpf == F_AUD) s.aud_found |= hit;
           else if (s.cmpf != F_NONE) s.str_ok |= hit << s.cmpf;
+          if constexpr (X) {
+            s.iss_len = s.cmpf == F_ISS ? s.pos : s.iss_len;
+            s.sub_len = s.cmpf == F_SUB ? s.pos : s.sub_len;
+            s.jti_len = s.cmpf == F_JTI ? s.pos : s.jti_len;
+            s.aud_len = s.cmpf == F_AUD && !s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud as one string
+          }
           end_value(s);
         }
       } else {
@@ -308,7 +356,8 @@ JG_CL_HD uint32_t sextet(uint32_t c) {
 }
 
 // jwt/jwt.go:117-199 on the scanned fields, in Validate's order
-JG_CL_HD uint8_t verdict(const Scan& s, const Expect& E) {
+template <bool X>
+JG_CL_HD uint8_t verdict(const ScanT<X>& s, const Expect& E) {
   int64_t iat = s.iat, exp = s.exp, nbf = s.nbf;
   if (iat == 0 && exp == 0 && nbf == 0) return JG_CL_NO_TIME;
   if (exp == 0) exp = (nbf > iat ? nbf : iat) + E.exp_leeway_s;
@@ -325,10 +374,14 @@ JG_CL_HD uint8_t verdict(const Scan& s, const Expect& E) {
   return JG_CL_OK;
 }
 
-template <class Src>
-JG_CL_HD uint8_t claims_decide(Src& src, uint32_t len, const Expect& E) {
+// The scan of one segment: claims_decide's code and, with X, the record.  The
+// state is a local of this function (handing it in by reference costs the
+// verdict-only kernel a third of its registers again).
+template <bool X, class Src>
+JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const Expect& E, jg_claims* out) {
+  if constexpr (X) *out = jg_claims{};                 // JG_CL_HOST: every byte zero
   if ((len & 3u) == 1u) return JG_CL_HOST;
-  Scan s;
+  ScanT<X> s;
   const uint32_t groups = (len + 3u) >> 2;
   for (uint32_t g = 0; g < groups && !s.bad; ++g) {
     const uint32_t w = src.word(g);
@@ -341,12 +394,42 @@ JG_CL_HD uint8_t claims_decide(Src& src, uint32_t len, const Expect& E) {
     // Go's strict decoding: the bits the last group does not use are zero
     if (nb < 3u && (trip & (nb == 1u ? 0xffffu : 0xffu))) return JG_CL_HOST;
     for (uint32_t k = 0; k < nb; ++k) {
+      if constexpr (X) s.dpos = 3u * g + k;
       step(s, (trip >> 16) & 0xffu, E);
       trip <<= 8;
     }
   }
   if (s.bad || s.st != ST_DONE) return JG_CL_HOST;
+  if constexpr (X) {
+    out->exp = s.exp;
+    out->nbf = s.nbf;
+    out->iat = s.iat;
+    out->iss_off = s.iss_off;
+    out->iss_len = s.iss_len;
+    out->sub_off = s.sub_off;
+    out->sub_len = s.sub_len;
+    out->jti_off = s.jti_off;
+    out->jti_len = s.jti_len;
+    out->aud_off = s.aud_off;
+    out->aud_len = s.aud_len;
+    out->aud_n = s.aud_n;
+    out->present = s.present;
+  }
   return verdict(s, E);
+}
+
+template <class Src>
+JG_CL_HD uint8_t claims_decide(Src& src, uint32_t len, const Expect& E) {
+  return scan_segment<false>(src, len, E, nullptr);
+}
+
+// claims_decide's code for the same input, always, and the registered claims
+// (include/jg.h jg_claims): filled for every code other than JG_CL_HOST, all
+// zero for JG_CL_HOST.  The scan's rules make the spans the Go strings: a
+// registered value with an escape or a byte >= 0x80, or named twice, is HOST.
+template <class Src>
+JG_CL_HD uint8_t claims_extract(Src& src, uint32_t len, const Expect& E, jg_claims* out) {
+  return scan_segment<true>(src, len, E, out);
 }
 
 }  // namespace jgclaims
@@ -356,4 +439,7 @@ JG_CL_HD uint8_t claims_decide(Src& src, uint32_t len, const Expect& E) {
 // code_out[i] = the jg_claim_code of jobs[i]; `expect` is a device jgclaims::Expect
 void launch_claims_scan(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
                         uint8_t* code_out, hipStream_t s);
+// ... and vals_out[i] = its registered claims (k_claims_extract)
+void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
+                           uint8_t* code_out, jg_claims* vals_out, hipStream_t s);
 #endif

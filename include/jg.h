@@ -349,6 +349,46 @@ typedef struct jg_expect {
 int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                    const jg_cjob* jobs, size_t njobs, const jg_expect* expect, uint8_t* code_out);
 
+/* ---- the scan that also returns the registered claims ----
+ * jg_claims_scan for callers that read the registered claims after the verdict
+ * (the subject to authorise, the expiry to cache until): the same jobs, the same
+ * `expect`, the same code_out[i] -- for the same input, always -- and with it
+ * vals_out[i], what the scan read of jwt.Claims (jwt/jwt.go:107-116):
+ *  - exp / nbf / iat: the payload's NumericDate values; 0 where the field is
+ *    absent or null (bit f of `present` tells 0 from absent);
+ *  - iss / sub / jti: the string's contents (between the quotes) as a byte span
+ *    [off, off + len) of the DECODED payload.  The scan decides only payloads
+ *    whose registered strings are ASCII without escapes, so those bytes are the
+ *    Go string: decode characters [4 (off / 3), 4 ceil((off + len) / 3)) of the
+ *    segment and cut the span out, no JSON parse.  "" has its bit set, len 0 and
+ *    off = the position after the opening quote; null has its bit clear and
+ *    off = len = 0;
+ *  - aud: the value's text from its first byte (" or [) through its last
+ *    (" or ]), and aud_n, the number of its string elements (1 for a string, k
+ *    for an array of k, 0 for []); the elements are the quoted runs of the span;
+ *  - present: bit f (1 iss, 2 sub, 3 jti, 4 aud, 5 exp, 6 nbf, 7 iat) is set
+ *    when the payload names field f with a value other than null.
+ * The record is filled for every code other than JG_CL_HOST, failures such as
+ * JG_CL_EXP included; for JG_CL_HOST all 64 bytes are zero and the caller reads
+ * the claims itself.
+ * Everything else is jg_claims_scan's: blocking, on the context's first device
+ * on the same stream of its own (extracts and scans of one context run one
+ * after the other, neither waits for nor delays a jg_submit), device buffers
+ * kept between calls, 0 / -1 / -2 as there, njobs == 0 returns 0 without
+ * touching the buffers.  vals_out == NULL with njobs > 0 is -1. */
+typedef struct jg_claims {
+  int64_t  exp, nbf, iat;        /* the payload's values; 0 where absent or null */
+  uint32_t iss_off, iss_len;     /* string contents (between the quotes), byte span in the DECODED payload */
+  uint32_t sub_off, sub_len;
+  uint32_t jti_off, jti_len;
+  uint32_t aud_off, aud_len;     /* the aud value's text, from its first byte (" or [) through its last (" or ]) */
+  uint32_t aud_n;                /* its string elements: 1 for a string, k for an array of k (0 for []) */
+  uint32_t present;              /* bit f (F_ISS=1 .. F_IAT=7 of claims.hpp): the field was named with a non-null value */
+} jg_claims;
+int jg_claims_extract(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                      const jg_cjob* jobs, size_t njobs, const jg_expect* expect,
+                      uint8_t* code_out, jg_claims* vals_out);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 
