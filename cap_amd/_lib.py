@@ -24,7 +24,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_submit", "jg_wait", "jg_set_chunk", "jg_set_zero_copy", "jg_set_table_budget", "jg_keys_wait_tables",
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
-           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract"]
+           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select"]
 
 
 class JgKey(ctypes.Structure):
@@ -86,6 +86,25 @@ assert ctypes.sizeof(JgClaims) == 64
 # bit f of jg_claims.present (F_ISS .. F_IAT of kernels/claims.hpp)
 F_ISS, F_SUB, F_JTI, F_AUD, F_EXP, F_NBF, F_IAT = range(1, 8)
 
+MAX_SELECT, SELECT_NAME_MAX = 8, 64          # JG_MAX_SELECT, JG_SELECT_NAME_MAX
+# jg_sel_type
+(SEL_ABSENT, SEL_STRING, SEL_STRING_RAW, SEL_NUMBER, SEL_TRUE, SEL_FALSE, SEL_NULL, SEL_ARRAY,
+ SEL_OBJECT) = range(9)
+
+
+class JgSelect(ctypes.Structure):
+    """jg_select: the caller's claim names, back to back in `names`"""
+    _fields_ = [("names", ctypes.c_void_p), ("n", ctypes.c_uint32), ("name_len", ctypes.c_uint32 * MAX_SELECT)]
+
+
+class JgSelected(ctypes.Structure):
+    """jg_selected: where the named top-level members of one payload lie"""
+    _fields_ = [("off", ctypes.c_uint32 * MAX_SELECT), ("len", ctypes.c_uint32 * MAX_SELECT),
+                ("type", ctypes.c_uint8 * MAX_SELECT), ("pad_", ctypes.c_uint8 * 8)]
+
+
+assert ctypes.sizeof(JgSelected) == 80
+
 _lib = None
 
 
@@ -127,6 +146,8 @@ def lib():
         L.jg_hash_batch.argtypes = [vp, vp, sz, vp, sz, vp]
         L.jg_claims_scan.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect), vp]
         L.jg_claims_extract.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect), vp, vp]
+        L.jg_claims_select.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                       ctypes.POINTER(JgSelect), vp, vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -276,9 +297,11 @@ class Context:
             raise JgError("jg_debug_max_upgrades failed")
 
     def debug_small_path(self, enable=None):
-        """jg_debug_small_path: small ECDSA submissions as one launch per curve (True, the
-        default) or through the batch chain (False; None leaves it); returns the
-        number of one-launch verifications enqueued so far.  Verdicts are identical."""
+        """jg_debug_small_path: small submissions of the one-launch classes (ECDSA on
+        P-256 / P-384 / P-521, EdDSA, RSA-2048 PKCS#1 v1.5) as one launch per (class,
+        key-table width) (True, the default) or through the batch chain (False; None
+        leaves it); returns the number of such launches enqueued so far -- the counter
+        counts launches, not tokens.  Verdicts are identical."""
         v = ctypes.c_uint64()
         if lib().jg_debug_small_path(self.h, -1 if enable is None else (1 if enable else 0), ctypes.byref(v)) != 0:
             raise JgError("jg_debug_small_path failed")
@@ -363,6 +386,49 @@ class Context:
         if rc != 0:
             raise JgError(f"jg_claims_extract rc={rc}: {self.error()}")
         return out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n])
+
+    def claims_select(self, arena_bytes, spans, expect, names, flags=0):
+        """jg_claims_select: claims_extract's codes and records and, per span, the
+        jg_selected record of the top-level members `names` (a list of bytes) name
+        -> (codes: bytes, vals: JgClaims array, sels: JgSelected array).  All three
+        outputs are poisoned with 0xee before the call."""
+        n = len(spans)
+        jobs = (JgCJob * max(1, n))()
+        for i, (off, ln) in enumerate(spans):
+            jobs[i].off, jobs[i].len, jobs[i].flags = off, ln, flags
+        auds = [bytes(a) for a in expect.get("audiences", [])]
+        strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
+        blob = b"".join(strs + auds)
+        e = JgExpect()
+        keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+        e.strs = ctypes.cast(keep, ctypes.c_void_p)
+        e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
+        e.naud = len(auds)
+        for k, a in enumerate(auds[:MAX_AUD]):
+            e.aud_len[k] = len(a)
+        e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
+        e.skew_ns = int(expect["skew_ns"])
+        e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
+        names = [bytes(x) for x in names]
+        nblob = b"".join(names)
+        sel = JgSelect()
+        nkeep = ctypes.create_string_buffer(nblob, max(1, len(nblob)))
+        sel.names = ctypes.cast(nkeep, ctypes.c_void_p)
+        sel.n = len(names)
+        for k, x in enumerate(names[:MAX_SELECT]):
+            sel.name_len[k] = len(x)
+        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
+        vals = (JgClaims * max(1, n))()
+        ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
+        sels = (JgSelected * max(1, n))()
+        ctypes.memset(sels, 0xee, ctypes.sizeof(sels))
+        buf = bytes(arena_bytes) or b"\0"
+        rc = lib().jg_claims_select(self.h, buf, len(arena_bytes), jobs, n, ctypes.byref(e), ctypes.byref(sel), out,
+                                    ctypes.cast(vals, ctypes.c_void_p), ctypes.cast(sels, ctypes.c_void_p))
+        if rc != 0:
+            raise JgError(f"jg_claims_select rc={rc}: {self.error()}")
+        return (out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n]),
+                (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n]))
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

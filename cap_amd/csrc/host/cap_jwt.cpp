@@ -1977,10 +1977,16 @@ RegisteredClaims claims_of_record(std::string_view seg, const jg_claims& v) {
 // payload segment, jg_claims) for a token the device accepted;
 // claims(chunk, i, jwt.Claims) for one the host path accepted.  chunk: which of
 // make_chunks(n, host_threads())'s ranges i lies in; one thread per chunk, in
-// index order.
-template <bool X, class Put>
+// index order.  M = kSelectMode (SelectBatch): the scan is jg_claims_select with
+// the caller's names (`select`; nullptr: a name list the ABI does not take, every
+// token takes the host path), the jg_selected records lie behind the jg_claims
+// records, record(...) also receives token i's jg_selected and claims(...) the
+// verified claims map of the host-path token.
+constexpr int kCheckMode = 0, kRegisteredMode = 1, kSelectMode = 2;
+template <int M, class Put>
 void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected& expected, CheckStats* stats,
-                Put&& put) {
+                Put&& put, const jg_select* select = nullptr) {
+  constexpr bool X = M >= kRegisteredMode;
   // a token that is not accepted carries no claims
   auto reject = [&](size_t c, size_t i, std::string&& err) {
     if constexpr (X) put.reject(c, i, std::move(err));
@@ -2006,6 +2012,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     }
   }
   scannable = scannable && strs.size() <= JG_EXPECT_MAX_BYTES;
+  if constexpr (M == kSelectMode) scannable = scannable && select != nullptr;
   ex.strs = (const uint8_t*)strs.data();
   {
     int64_t s = now / kSecond, ns = now % kSecond;
@@ -2024,11 +2031,13 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   // Both arrays live in one pinned block of the engine's pool (DMA at link
   // speed, no page faults in steady state).
   Engine& eng = ks_->engine();
-  const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | codes
-  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + rec_bytes + 16);
+  const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | selected | codes
+  const size_t sel_bytes = M == kSelectMode ? n * sizeof(jg_selected) : 0;
+  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + rec_bytes + sel_bytes + 16);
   jg_cjob* const jobs = (jg_cjob*)scanbuf.get();
   jg_claims* const recs = (jg_claims*)(scanbuf.get() + n * sizeof(jg_cjob));
-  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes;
+  jg_selected* const sels = (jg_selected*)(scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes);
+  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes + sel_bytes;
   std::memset(code, JG_CL_HOST, n);
   bool have_jobs = false;
   bool scan_failed = false;
@@ -2055,7 +2064,8 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     });
     pt.lap("scan-jobs");
     try {
-      if constexpr (X) eng.claims_extract(V.arena, V.arena_len, jobs, n, &ex, code, recs, true);
+      if constexpr (M == kSelectMode) eng.claims_select(V.arena, V.arena_len, jobs, n, &ex, select, code, recs, sels, true);
+      else if constexpr (X) eng.claims_extract(V.arena, V.arena_len, jobs, n, &ex, code, recs, true);
       else eng.claims_scan(V.arena, V.arena_len, jobs, n, &ex, code, true);
     } catch (const DeviceError& e) {
       // as a failed verify: the tokens the scan carried get its error (no
@@ -2096,8 +2106,9 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
         if constexpr (X) {
           RegisteredClaims rc;
           Result v = validate_claims(r.claims, t.view(), expected, now, &rc);
-          if (v.ok) put.claims(c, i, std::move(rc));
-          else reject(c, i, std::move(v.err));
+          if (!v.ok) reject(c, i, std::move(v.err));
+          else if constexpr (M == kSelectMode) put.claims(c, i, std::move(rc), r.claims);
+          else put.claims(c, i, std::move(rc));
         } else {
           Result v = validate_claims(r.claims, t.view(), expected, now);
           put(i, v.ok, std::move(v.err));
@@ -2113,6 +2124,8 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
       if constexpr (X) {
         // the payload segment ends the signing input; its length is the job's
         if (code[i] != JG_CL_OK) reject(c, i, std::string(claim_code_error(code[i])));
+        else if constexpr (M == kSelectMode)
+          put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i], sels[i]);
         else
           put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i]);
       } else {
@@ -2138,7 +2151,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
 std::vector<CheckResult> Validator::CheckBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
                                                CheckStats* stats) {
   std::vector<CheckResult> out(tokens.size());
-  check_core<false>(ks_, tokens, expected, stats, [&](size_t i, bool ok, std::string&& err) {
+  check_core<kCheckMode>(ks_, tokens, expected, stats, [&](size_t i, bool ok, std::string&& err) {
     out[i].ok = ok;
     out[i].err = std::move(err);
   });
@@ -2262,7 +2275,7 @@ struct ColumnSink {
 std::vector<RegisteredResult> Validator::RegisteredBatch(const std::vector<std::string_view>& tokens,
                                                          const Expected& expected, CheckStats* stats) {
   std::vector<RegisteredResult> out(tokens.size());
-  check_core<true>(ks_, tokens, expected, stats, RowSink{out});
+  check_core<kRegisteredMode>(ks_, tokens, expected, stats, RowSink{out});
   return out;
 }
 
@@ -2270,7 +2283,188 @@ void Validator::RegisteredCols(const std::vector<std::string_view>& tokens, cons
                                const RegisteredColumns& out, CheckStats* stats) {
   const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
   ColumnSink sink(out, ch);
-  check_core<true>(ks_, tokens, expected, stats, sink);
+  check_core<kRegisteredMode>(ks_, tokens, expected, stats, sink);
+  PhaseTimer pt("check");
+  sink.finish();
+  pt.lap("columns");
+}
+
+namespace {
+// The caller's names as the scan takes them (jg_select): equal names share a
+// slot.  usable == false: the ABI does not take the list and every token goes
+// the host path.
+struct SelectNames {
+  std::string bytes;
+  jg_select abi{};
+  std::vector<int> slot;                           // names[k] is slot[k] of a jg_selected
+  bool usable = true;
+  explicit SelectNames(const std::vector<std::string>& names) : slot(names.size(), -1) {
+    std::vector<std::string_view> uniq;
+    for (size_t k = 0; k < names.size(); ++k) {
+      const std::string& nm = names[k];
+      if (nm.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim name holds a NUL byte");
+      if (nm.empty() || nm.size() > JG_SELECT_NAME_MAX) usable = false;
+      for (unsigned char c : nm)
+        if (c < 0x20 || c > 0x7e || c == '"' || c == '\\') usable = false;
+      size_t u = 0;
+      while (u < uniq.size() && uniq[u] != nm) ++u;
+      if (u == uniq.size()) uniq.push_back(nm);
+      slot[k] = (int)u;
+    }
+    if (uniq.size() > JG_MAX_SELECT) usable = false;
+    if (!usable) return;
+    for (size_t u = 0; u < uniq.size(); ++u) {
+      abi.name_len[u] = (uint32_t)uniq[u].size();
+      bytes += uniq[u];
+    }
+    abi.n = (uint32_t)uniq.size();
+    abi.names = (const uint8_t*)bytes.data();
+  }
+  const jg_select* select() const { return usable ? &abi : nullptr; }
+};
+
+// The claims-map entry a slot of the scan's record stands for.  A string whose
+// bytes are ASCII is cut out of the decoded payload; a number, a string with
+// bytes >= 0x80, an array or an object is parsed from its own span (the parser
+// the claims map is read with, so numbers and invalid UTF-8 come out the same).
+std::optional<json::Value> value_of_slot(std::string_view seg, const jg_selected& q, int slot) {
+  std::optional<json::Value> out;
+  const uint8_t type = q.type[slot];
+  if (type == JG_SEL_ABSENT) return out;
+  json::Value& v = out.emplace();
+  std::string text;
+  switch (type) {
+    case JG_SEL_NULL: break;
+    case JG_SEL_TRUE:
+    case JG_SEL_FALSE:
+      v.kind = json::Value::Bool;
+      v.b = type == JG_SEL_TRUE;
+      break;
+    case JG_SEL_STRING:
+      append_span(text, seg, q.off[slot], q.len[slot]);
+      v.kind = json::Value::String;
+      v.str = std::string_view(text);
+      break;
+    default: {
+      append_span(text, seg, q.off[slot], q.len[slot]);
+      std::string err;
+      if (!json::parse(text, &v, &err)) throw std::logic_error("capjwt: the claims scan returned a span that does not parse: " + err);
+    }
+  }
+  return out;
+}
+
+uint8_t sel_type_of(const json::Value& v) {
+  switch (v.kind) {
+    case json::Value::Null: return JG_SEL_NULL;
+    case json::Value::Bool: return v.b ? JG_SEL_TRUE : JG_SEL_FALSE;
+    case json::Value::Number: return JG_SEL_NUMBER;
+    case json::Value::String: return JG_SEL_STRING;
+    case json::Value::Array: return JG_SEL_ARRAY;
+    default: return JG_SEL_OBJECT;
+  }
+}
+
+struct SelectRowSink {                             // SelectBatch: one SelectResult per token
+  std::vector<SelectResult>& out;
+  const std::vector<std::string>& names;
+  const SelectNames& N;
+  void reject(size_t, size_t i, std::string&& err) { out[i].err = std::move(err); }
+  void record(size_t, size_t i, std::string_view seg, const jg_claims& v, const jg_selected& q) {
+    out[i].ok = true;
+    out[i].claims = claims_of_record(seg, v);
+    out[i].values.resize(names.size());
+    for (size_t k = 0; k < names.size(); ++k) out[i].values[k] = value_of_slot(seg, q, N.slot[k]);
+  }
+  void claims(size_t, size_t i, RegisteredClaims&& c, const json::Value& all) {
+    out[i].ok = true;
+    out[i].claims = std::move(c);
+    out[i].values.resize(names.size());
+    for (size_t k = 0; k < names.size(); ++k)
+      if (const json::Value* m = all.get(names[k])) out[i].values[k] = *m;
+  }
+};
+
+// SelectCols: ColumnSink for the registered columns; per name the type and the
+// number are written in place and the text goes to the merge thread's part
+struct SelectColumnSink {
+  ColumnSink reg;
+  const SelectColumns& S;
+  const std::vector<std::string>& names;
+  const SelectNames& N;
+  const Chunks& ch;
+  std::vector<std::vector<std::string>> text;      // [chunk][name]
+  SelectColumnSink(const SelectColumns& s, const std::vector<std::string>& nm, const SelectNames& sn, const Chunks& chunks)
+      : reg(s.reg, chunks), S(s), names(nm), N(sn), ch(chunks),
+        text(chunks.count(), std::vector<std::string>(nm.size())) {}
+  void cell(size_t c, size_t i, size_t k, const json::Value* v, uint8_t type) {
+    std::string& T = text[c][k];
+    if (v) {
+      if (v->kind == json::Value::String) T.append(v->str.data(), v->str.size());
+      else if (v->kind == json::Value::Array || v->kind == json::Value::Object) T += json::marshal(*v);
+    }
+    S.names[k].type[i] = type;
+    S.names[k].num[i] = v && v->kind == json::Value::Number ? v->num : 0.0;
+    S.names[k].text_off[i + 1] = (uint32_t)T.size();
+  }
+  void reject(size_t c, size_t i, std::string&& err) {
+    reg.reject(c, i, std::move(err));
+    for (size_t k = 0; k < names.size(); ++k) cell(c, i, k, nullptr, JG_SEL_ABSENT);
+  }
+  void record(size_t c, size_t i, std::string_view seg, const jg_claims& v, const jg_selected& q) {
+    reg.record(c, i, seg, v);
+    for (size_t k = 0; k < names.size(); ++k) {
+      const int slot = N.slot[k];
+      if (q.type[slot] == JG_SEL_STRING) {         // the common case: straight from the payload into the part
+        append_span(text[c][k], seg, q.off[slot], q.len[slot]);
+        cell(c, i, k, nullptr, JG_SEL_STRING);
+        continue;
+      }
+      const std::optional<json::Value> val = value_of_slot(seg, q, slot);
+      cell(c, i, k, val ? &*val : nullptr, q.type[slot]);
+    }
+  }
+  void claims(size_t c, size_t i, RegisteredClaims&& cl, const json::Value& all) {
+    reg.claims(c, i, std::move(cl));
+    for (size_t k = 0; k < names.size(); ++k) {
+      const json::Value* m = all.get(names[k]);
+      cell(c, i, k, m, m ? sel_type_of(*m) : (uint8_t)JG_SEL_ABSENT);
+    }
+  }
+  void finish() {
+    reg.finish();
+    const size_t nc = text.size();
+    for (size_t k = 0; k < names.size(); ++k) {
+      std::vector<size_t> base(nc + 1, 0);
+      for (size_t c = 0; c < nc; ++c) base[c + 1] = base[c] + text[c][k].size();
+      char* const data = (char*)S.alloc_text(k, base[nc]);
+      uint32_t* const off = S.names[k].text_off;
+      off[0] = 0;
+      run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
+        const std::string& src = text[c][k];
+        if (!src.empty()) std::memcpy(data + base[c], src.data(), src.size());
+        for (size_t i = lo; i < hi; ++i) off[i + 1] += (uint32_t)base[c];
+      });
+    }
+  }
+};
+}  // namespace
+
+std::vector<SelectResult> Validator::SelectBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                                 const std::vector<std::string>& names, CheckStats* stats) {
+  const SelectNames N(names);
+  std::vector<SelectResult> out(tokens.size());
+  check_core<kSelectMode>(ks_, tokens, expected, stats, SelectRowSink{out, names, N}, N.select());
+  return out;
+}
+
+void Validator::SelectCols(const std::vector<std::string_view>& tokens, const Expected& expected,
+                           const std::vector<std::string>& names, const SelectColumns& out, CheckStats* stats) {
+  if (out.names.size() != names.size()) throw std::invalid_argument("capjwt: SelectCols: one column set per name");
+  const SelectNames N(names);
+  const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
+  SelectColumnSink sink(out, names, N, ch);
+  check_core<kSelectMode>(ks_, tokens, expected, stats, sink, N.select());
   PhaseTimer pt("check");
   sink.finish();
   pt.lap("columns");
@@ -2279,7 +2473,7 @@ void Validator::RegisteredCols(const std::vector<std::string_view>& tokens, cons
 std::vector<uint8_t> Validator::CheckVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
                                               CheckStats* stats) {
   std::vector<uint8_t> ok(tokens.size(), 0);
-  check_core<false>(ks_, tokens, expected, stats, [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
+  check_core<kCheckMode>(ks_, tokens, expected, stats, [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
   return ok;
 }
 
@@ -2326,6 +2520,24 @@ void Engine::claims_extract(const uint8_t* arena, size_t arena_len, const void* 
   if (rc == -1)
     throw std::logic_error(std::string("capjwt: jg_claims_extract rejected the host's jobs: ") + jg_last_error(ctx_));
   if (rc != 0) fail_device(std::string("capjwt: jg_claims_extract: ") + jg_last_error(ctx_));
+}
+
+// ... and jg_claims_select (SelectBatch)
+extern "C" __attribute__((weak)) int jg_claims_select(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
+                                                      const jg_expect*, const jg_select*, uint8_t*, jg_claims*,
+                                                      jg_selected*);
+
+void Engine::claims_select(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
+                           const void* select, uint8_t* codes, void* vals, void* sels, bool inside_verify) {
+  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
+  if (!inside_verify) life.lock();
+  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
+  if (!jg_claims_select) fail_device("capjwt: jg_claims_select: not provided by the loaded verifier library");
+  const int rc = jg_claims_select(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect,
+                                  (const jg_select*)select, codes, (jg_claims*)vals, (jg_selected*)sels);
+  if (rc == -1)
+    throw std::logic_error(std::string("capjwt: jg_claims_select rejected the host's jobs: ") + jg_last_error(ctx_));
+  if (rc != 0) fail_device(std::string("capjwt: jg_claims_select: ") + jg_last_error(ctx_));
 }
 
 namespace {

@@ -199,6 +199,10 @@ class Engine {
   // ... and vals[i] = the jg_claims record of job i (jg_claims_extract)
   void claims_extract(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
                       uint8_t* codes, void* vals, bool inside_verify = false);
+  // ... and sels[i] = the jg_selected record of the members `select` (a
+  // jg_select) names (jg_claims_select)
+  void claims_select(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
+                     const void* select, uint8_t* codes, void* vals, void* sels, bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -460,6 +464,33 @@ struct RegisteredColumns {
   std::function<void*(Var which, size_t bytes)> alloc;
 };
 
+// RegisteredResult and the claims the caller named: values[k] is what
+// ValidateBatch's claims map holds under names[k] (nullopt: the map has no such
+// key; a JSON null is a Value of kind Null).  A rejected token carries none.
+struct SelectResult {
+  bool ok = false;
+  std::string err;
+  RegisteredClaims claims;
+  std::vector<std::optional<json::Value>> values;     // one per name
+};
+// SelectBatch as columns (SelectBlob): RegisteredColumns plus, per name, the
+// value's type, its number and its text.  Rows of a rejected token are empty.
+struct SelectColumns {
+  RegisteredColumns reg;
+  struct Name {
+    uint8_t* type = nullptr;        // n bytes of jg_sel_type (include/jg.h); a token the host path decided
+                                    // reports JG_SEL_STRING for any string
+    double* num = nullptr;          // n float64: the JG_SEL_NUMBER's value, else 0
+    uint32_t* text_off = nullptr;   // n + 1 offsets into the name's text column
+  };
+  std::vector<Name> names;          // one per name, in the caller's order
+  // The text column of name k, sized by the call: a string's UTF-8 bytes, or
+  // json::marshal(value) for an array or an object (on both paths, so the bytes
+  // do not depend on which path decided); empty for every other type.  Called
+  // once per name, from the calling thread.
+  std::function<void*(size_t k, size_t bytes)> alloc_text;
+};
+
 class Validator {
  public:
   explicit Validator(KeySet* ks) : ks_(ks) {}
@@ -491,6 +522,24 @@ class Validator {
   // threads that merge the scan's records (RegisteredBlob)
   void RegisteredCols(const std::vector<std::string_view>& tokens, const Expected& expected,
                       const RegisteredColumns& out, CheckStats* stats = nullptr);
+  // RegisteredBatch plus top-level claims outside the registered seven, by name
+  // (scope, roles, tenant, nonce, azp, auth_time, ...): ok / err / claims are
+  // RegisteredBatch's, token for token, and values[k] of an accepted token is
+  // ValidateBatch's claims-map entry under names[k], exactly (case-sensitive).
+  // The scan latches where each named member's value lies (jg_claims_select); a
+  // string is cut out of the decoded payload, a number, array or object is
+  // parsed from its own few bytes -- no claims map.  A token the scan leaves to
+  // the host reads its verified claims map.  A name list the scan does not take
+  // (more than JG_MAX_SELECT distinct names, a name that is empty, over
+  // JG_SELECT_NAME_MAX bytes, or holds a quote, a backslash or a byte outside
+  // printable ASCII) sends every token to the host path; equal names share a
+  // slot.  Throws std::invalid_argument for a name with a NUL byte.
+  std::vector<SelectResult> SelectBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                        const std::vector<std::string>& names, CheckStats* stats = nullptr);
+  // SelectBatch as columns, built by the host threads that merge the scan's
+  // records (SelectBlob); out.names.size() == names.size()
+  void SelectCols(const std::vector<std::string_view>& tokens, const Expected& expected,
+                  const std::vector<std::string>& names, const SelectColumns& out, CheckStats* stats = nullptr);
  private:
   KeySet* ks_;
 };

@@ -49,6 +49,74 @@ py::tuple result_py(const Result& r) {
   return py::make_tuple(py::none(), py::str(r.err));
 }
 
+// go-jose's jwt.Claims of an accepted token as RegisteredBatch / SelectBatch return it
+py::dict claims_py(const RegisteredClaims& c) {
+  auto date = [](const std::optional<int64_t>& d) -> py::object {
+    return d ? py::object(py::int_(*d)) : py::object(py::none());
+  };
+  py::dict d;
+  d["iss"] = py::str(c.Issuer);
+  d["sub"] = py::str(c.Subject);
+  d["jti"] = py::str(c.ID);
+  py::list aud;
+  for (const auto& a : c.Audience) aud.append(py::str(a));
+  d["aud"] = aud;
+  d["exp"] = date(c.Expiry);
+  d["nbf"] = date(c.NotBefore);
+  d["iat"] = date(c.IssuedAt);
+  return d;
+}
+
+// a bytes object the host threads write into: nothing is copied afterwards
+py::bytes fresh_bytes(size_t bytes) {
+  PyObject* o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)bytes);
+  if (!o) throw py::error_already_set();
+  return py::reinterpret_steal<py::bytes>(o);
+}
+void* bytes_mem(py::bytes& b) { return (void*)PyBytes_AS_STRING(b.ptr()); }
+
+// RegisteredColumns over bytes objects (RegisteredBlob, SelectBlob)
+struct RegisteredBlobCols {
+  py::bytes ok, present, exp, nbf, iat;
+  py::bytes off[4];
+  py::bytes var[5];
+  RegisteredColumns R;
+  explicit RegisteredBlobCols(size_t n)
+      : ok(fresh_bytes(n)), present(fresh_bytes(n)), exp(fresh_bytes(8 * n)), nbf(fresh_bytes(8 * n)),
+        iat(fresh_bytes(8 * n)),
+        off{fresh_bytes(4 * (n + 1)), fresh_bytes(4 * (n + 1)), fresh_bytes(4 * (n + 1)), fresh_bytes(4 * (n + 1))} {
+    R.ok = (uint8_t*)bytes_mem(ok);
+    R.present = (uint8_t*)bytes_mem(present);
+    R.exp = (int64_t*)bytes_mem(exp);
+    R.nbf = (int64_t*)bytes_mem(nbf);
+    R.iat = (int64_t*)bytes_mem(iat);
+    R.iss_off = (uint32_t*)bytes_mem(off[0]);
+    R.sub_off = (uint32_t*)bytes_mem(off[1]);
+    R.jti_off = (uint32_t*)bytes_mem(off[2]);
+    R.aud_tok = (uint32_t*)bytes_mem(off[3]);
+    R.alloc = [this](RegisteredColumns::Var which, size_t bytes) {
+      py::gil_scoped_acquire gil;
+      var[which] = fresh_bytes(bytes);
+      return bytes_mem(var[which]);
+    };
+  }
+  RegisteredBlobCols(const RegisteredBlobCols&) = delete;
+  RegisteredBlobCols& operator=(const RegisteredBlobCols&) = delete;
+  py::dict dict() {
+    py::dict d;
+    d["ok"] = ok;
+    d["present"] = present;
+    d["exp"] = exp;
+    d["nbf"] = nbf;
+    d["iat"] = iat;
+    d["iss"] = py::make_tuple(off[0], var[RegisteredColumns::ISS]);
+    d["sub"] = py::make_tuple(off[1], var[RegisteredColumns::SUB]);
+    d["jti"] = py::make_tuple(off[2], var[RegisteredColumns::JTI]);
+    d["aud"] = py::make_tuple(off[3], var[RegisteredColumns::AUD_OFF], var[RegisteredColumns::AUD]);
+    return d;
+  }
+};
+
 py::list results_py(const Results& rs) {
   py::list l;
   for (const auto& r : rs) l.append(result_py(r));
@@ -490,27 +558,10 @@ PYBIND11_MODULE(_capjwt_host, m) {
           py::gil_scoped_release rel;
           rs = s.v->RegisteredBatch(views(v), e, &st);
         }
-        auto date = [](const std::optional<int64_t>& d) -> py::object {
-          return d ? py::object(py::int_(*d)) : py::object(py::none());
-        };
         py::list out(rs.size());
         for (size_t i = 0; i < rs.size(); ++i) {
-          if (!rs[i].ok) {
-            out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
-            continue;
-          }
-          const RegisteredClaims& c = rs[i].claims;
-          py::dict d;
-          d["iss"] = py::str(c.Issuer);
-          d["sub"] = py::str(c.Subject);
-          d["jti"] = py::str(c.ID);
-          py::list aud;
-          for (const auto& a : c.Audience) aud.append(py::str(a));
-          d["aud"] = aud;
-          d["exp"] = date(c.Expiry);
-          d["nbf"] = date(c.NotBefore);
-          d["iat"] = date(c.IssuedAt);
-          out[i] = py::make_tuple(d, py::none());
+          if (!rs[i].ok) out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
+          else out[i] = py::make_tuple(claims_py(rs[i].claims), py::none());
         }
         return py::make_tuple(out, st.scanned, st.host);
       })
@@ -520,14 +571,6 @@ PYBIND11_MODULE(_capjwt_host, m) {
         char* bp = nullptr;
         Py_ssize_t bn = 0;
         if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
-        // the columns are bytes objects from the start: the host threads write
-        // into them, nothing is copied afterwards
-        auto fresh = [](size_t bytes) {
-          PyObject* o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)bytes);
-          if (!o) throw py::error_already_set();
-          return py::reinterpret_steal<py::bytes>(o);
-        };
-        auto mem = [](py::bytes& b) { return (void*)PyBytes_AS_STRING(b.ptr()); };
         const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
         auto t0 = std::chrono::steady_clock::now();
         auto lap = [&](const char* what) {
@@ -539,41 +582,91 @@ PYBIND11_MODULE(_capjwt_host, m) {
         };
         auto toks = split_lines(bp, (size_t)bn);
         lap("split");
+        // the columns are bytes objects from the start
+        RegisteredBlobCols C(toks.size());
+        CheckStats st;
+        {
+          py::gil_scoped_release rel;
+          s.v->RegisteredCols(toks, e, C.R, &st);
+        }
+        lap("registered");
+        return py::make_tuple(C.dict(), st.scanned, st.host);
+      })
+      .def("select_batch", [](PyValidator& s, py::sequence toks, std::vector<std::string> names, const Expected& e) {
+        // registered_batch with the claims `names` name:
+        // ([(claims dict or None, {name: value} or None, error or None)], scanned, host)
+        auto v = as_strings(toks);
+        std::vector<SelectResult> rs;
+        CheckStats st;
+        {
+          py::gil_scoped_release rel;
+          rs = s.v->SelectBatch(views(v), e, names, &st);
+        }
+        py::list out(rs.size());
+        for (size_t i = 0; i < rs.size(); ++i) {
+          if (!rs[i].ok) {
+            out[i] = py::make_tuple(py::none(), py::none(), py::str(rs[i].err));
+            continue;
+          }
+          py::dict vals;
+          for (size_t k = 0; k < names.size(); ++k)
+            if (rs[i].values[k]) vals[py::str(names[k])] = to_py(*rs[i].values[k]);
+          out[i] = py::make_tuple(claims_py(rs[i].claims), vals, py::none());
+        }
+        return py::make_tuple(out, st.scanned, st.host);
+      })
+      .def("select_blob", [](PyValidator& s, py::bytes blob, std::vector<std::string> names, const Expected& e) {
+        // registered_blob with, per name, the value's type / number / text columns
+        char* bp = nullptr;
+        Py_ssize_t bn = 0;
+        if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+        const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](const char* what) {
+          if (!trace) return;
+          const auto t1 = std::chrono::steady_clock::now();
+          std::fprintf(stderr, "[capjwt] sblob %-12s %8.2f ms\n", what,
+                       std::chrono::duration<double, std::milli>(t1 - t0).count());
+          t0 = t1;
+        };
+        auto toks = split_lines(bp, (size_t)bn);
+        lap("split");
         const size_t n = toks.size();
-        py::bytes ok = fresh(n), present = fresh(n), exp = fresh(8 * n), nbf = fresh(8 * n), iat = fresh(8 * n);
-        py::bytes off[4] = {fresh(4 * (n + 1)), fresh(4 * (n + 1)), fresh(4 * (n + 1)), fresh(4 * (n + 1))};
-        py::bytes var[5];
-        RegisteredColumns R;
-        R.ok = (uint8_t*)mem(ok);
-        R.present = (uint8_t*)mem(present);
-        R.exp = (int64_t*)mem(exp);
-        R.nbf = (int64_t*)mem(nbf);
-        R.iat = (int64_t*)mem(iat);
-        R.iss_off = (uint32_t*)mem(off[0]);
-        R.sub_off = (uint32_t*)mem(off[1]);
-        R.jti_off = (uint32_t*)mem(off[2]);
-        R.aud_tok = (uint32_t*)mem(off[3]);
-        R.alloc = [&](RegisteredColumns::Var which, size_t bytes) {
+        RegisteredBlobCols C(n);
+        std::vector<py::bytes> type(names.size()), num(names.size()), text_off(names.size()), text(names.size());
+        SelectColumns S;
+        S.reg = C.R;
+        S.names.resize(names.size());
+        for (size_t k = 0; k < names.size(); ++k) {
+          type[k] = fresh_bytes(n);
+          num[k] = fresh_bytes(8 * n);
+          text_off[k] = fresh_bytes(4 * (n + 1));
+          S.names[k].type = (uint8_t*)bytes_mem(type[k]);
+          S.names[k].num = (double*)bytes_mem(num[k]);
+          S.names[k].text_off = (uint32_t*)bytes_mem(text_off[k]);
+        }
+        S.alloc_text = [&](size_t k, size_t bytes) {
           py::gil_scoped_acquire gil;
-          var[which] = fresh(bytes);
-          return mem(var[which]);
+          text[k] = fresh_bytes(bytes);
+          return bytes_mem(text[k]);
         };
         CheckStats st;
         {
           py::gil_scoped_release rel;
-          s.v->RegisteredCols(toks, e, R, &st);
+          s.v->SelectCols(toks, e, names, S, &st);
         }
-        lap("registered");
-        py::dict d;
-        d["ok"] = ok;
-        d["present"] = present;
-        d["exp"] = exp;
-        d["nbf"] = nbf;
-        d["iat"] = iat;
-        d["iss"] = py::make_tuple(off[0], var[RegisteredColumns::ISS]);
-        d["sub"] = py::make_tuple(off[1], var[RegisteredColumns::SUB]);
-        d["jti"] = py::make_tuple(off[2], var[RegisteredColumns::JTI]);
-        d["aud"] = py::make_tuple(off[3], var[RegisteredColumns::AUD_OFF], var[RegisteredColumns::AUD]);
+        lap("select");
+        py::dict d = C.dict();
+        py::list sel;
+        for (size_t k = 0; k < names.size(); ++k) {
+          py::dict c;
+          c["type"] = type[k];
+          c["num"] = num[k];
+          c["text_off"] = text_off[k];
+          c["text"] = text[k];
+          sel.append(c);
+        }
+        d["sel"] = sel;
         return py::make_tuple(d, st.scanned, st.host);
       })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,

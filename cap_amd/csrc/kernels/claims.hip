@@ -85,7 +85,63 @@ __global__ void __launch_bounds__(kBlock) k_claims_extract(const uint8_t* __rest
   o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
 }
 
+// k_claims_extract that also latches where the caller's named top-level
+// members lie: sel_out[i] is token i's jg_selected (80 bytes), five 16-byte
+// stores.  The resolved names sit in LDS beside the Expected; a depth-1 key is
+// compared with them byte by byte from there.
+__global__ void __launch_bounds__(kBlock) k_claims_select(const uint8_t* __restrict__ arena,
+                                                          const jg_cjob* __restrict__ jobs, int64_t n,
+                                                          const Expect* __restrict__ expect,
+                                                          const Select* __restrict__ select,
+                                                          uint8_t* __restrict__ code_out,
+                                                          jg_claims* __restrict__ vals_out,
+                                                          jg_selected* __restrict__ sel_out) {
+  __shared__ Expect E;
+  __shared__ Select S;
+  {
+    static_assert(sizeof(Select) % 4 == 0, "Select is copied by words");
+    const uint32_t* src = (const uint32_t*)expect;
+    uint32_t* dst = (uint32_t*)&E;
+    for (uint32_t k = threadIdx.x; k < sizeof(Expect) / 4; k += kBlock) dst[k] = src[k];
+    const uint32_t* ssrc = (const uint32_t*)select;
+    uint32_t* sdst = (uint32_t*)&S;
+    for (uint32_t k = threadIdx.x; k < sizeof(Select) / 4; k += kBlock) sdst[k] = ssrc[k];
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const jg_cjob J = jobs[i];
+  WordSrc src;
+  src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
+  src.shift8 = 8u * (uint32_t)(J.off & 3);
+  src.cur = src.aligned[0];
+  jg_claims v;                                  // fields and constant indices only: both stay in registers
+  jg_selected q;
+  code_out[i] = claims_select(src, J.len, E, S, &v, &q);
+  uint4* o = (uint4*)(vals_out + i);
+  o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
+  o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
+  o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
+  o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
+  static_assert(sizeof(jg_selected) == 80, "the record is five 16-byte stores");
+  uint4* t = (uint4*)(sel_out + i);
+  t[0] = make_uint4(q.off[0], q.off[1], q.off[2], q.off[3]);
+  t[1] = make_uint4(q.off[4], q.off[5], q.off[6], q.off[7]);
+  t[2] = make_uint4(q.len[0], q.len[1], q.len[2], q.len[3]);
+  t[3] = make_uint4(q.len[4], q.len[5], q.len[6], q.len[7]);
+  t[4] = make_uint4(q.type[0] | (uint32_t)q.type[1] << 8 | (uint32_t)q.type[2] << 16 | (uint32_t)q.type[3] << 24,
+                    q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
+}
+
 }  // namespace
+
+void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
+                          const Select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
+                          hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_claims_select, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs, n,
+                     expect, select, code_out, vals_out, sel_out);
+}
 
 void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
                            uint8_t* code_out, jg_claims* vals_out, hipStream_t s) {

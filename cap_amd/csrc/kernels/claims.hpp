@@ -20,9 +20,16 @@
 // arrays indexed at run time, nothing that would go to scratch.
 //
 // claims_extract() is the same scan with extraction switched on at compile
-// time (ScanT<true>): the same code, plus a jg_claims record of the registered
-// claims -- the dates as numbers, iss / sub / jti / aud as byte spans into the
-// decoded payload.  ScanT<false> is the verdict-only scan, unchanged.
+// time (ScanT<kExtract>): the same code, plus a jg_claims record of the
+// registered claims -- the dates as numbers, iss / sub / jti / aud as byte spans
+// into the decoded payload.  ScanT<kVerdict> is the verdict-only scan, unchanged.
+//
+// claims_select() is a third mode of the same scan (ScanT<kSelect>): the code
+// and the record of claims_extract, plus a jg_selected record of up to
+// JG_MAX_SELECT top-level members the caller names (Select, in LDS beside
+// Expect): a candidate mask over the names is armed when a depth-1 key opens,
+// narrowed per key byte and resolved at the closing quote; the value's first
+// byte latches the slot's offset and type, its end the length.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -89,6 +96,44 @@ inline bool resolve(const jg_expect& x, Expect* E) {
   return true;
 }
 
+// The caller's claim names as the selecting scan reads them (a device buffer
+// copied to LDS beside Expect)
+struct Select {
+  uint32_t n;
+  uint16_t len[JG_MAX_SELECT];
+  uint16_t off[JG_MAX_SELECT];
+  uint8_t bytes[JG_MAX_SELECT * JG_SELECT_NAME_MAX];
+};
+
+// Fills *S from the ABI's jg_select.  False: more than JG_MAX_SELECT names, a
+// name that is empty or longer than JG_SELECT_NAME_MAX, a name byte outside
+// 0x20..0x7e or equal to " or \, two equal names.
+inline bool resolve_select(const jg_select& x, Select* S) {
+  if (x.n > JG_MAX_SELECT) return false;
+  uint32_t o = 0;
+  for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
+    const uint32_t l = k < x.n ? x.name_len[k] : 0u;
+    if (k < x.n && (l == 0 || l > JG_SELECT_NAME_MAX || !x.names)) return false;
+    S->len[k] = (uint16_t)l;
+    S->off[k] = (uint16_t)o;
+    for (uint32_t b = 0; b < l; ++b) {
+      const uint8_t c = x.names[o + b];
+      if (c < 0x20u || c > 0x7eu || c == '"' || c == '\\') return false;
+      S->bytes[o + b] = c;
+    }
+    for (uint32_t j = 0; j < k; ++j) {
+      if (S->len[j] != l || l == 0) continue;
+      uint32_t b = 0;
+      while (b < l && S->bytes[S->off[j] + b] == S->bytes[o + b]) ++b;
+      if (b == l) return false;
+    }
+    o += l;
+  }
+  for (uint32_t b = o; b < sizeof S->bytes; ++b) S->bytes[b] = 0;
+  S->n = x.n;
+  return true;
+}
+
 enum : uint32_t {
   ST_START, ST_VALUE, ST_ARR_FIRST, ST_OBJ_FIRST, ST_OBJ_KEY, ST_COLON, ST_AFTER, ST_STR,
   ST_NUM_MINUS, ST_NUM_ZERO, ST_NUM_INT, ST_NUM_DOT, ST_NUM_FRAC, ST_LIT, ST_DONE
@@ -112,9 +157,28 @@ struct Extract {
 };
 struct NoExtract {};
 
-// X: also record the claim values (Extract); X = false is the verdict-only scan
-template <bool X>
-struct ScanT : std::conditional_t<X, Extract, NoExtract> {
+// What the selecting form (claims_select) keeps beside Extract's: which of the
+// caller's names the depth-1 key read so far can still be, the slot of the
+// member whose value comes next, and per slot where that value lies.  The slot
+// arrays are only ever touched by constant-trip loops over all eight slots
+// (selects on `slot == k`), so they stay registers like the scalars.
+struct SelState {
+  uint32_t kcand = 0;               // bit k: the depth-1 key so far is a prefix of name k
+  uint32_t ksel = 0;                // slot + 1 of the depth-1 member being read; 0: not selected
+  uint32_t hi = 0;                  // the string value being read holds a byte >= 0x80
+  uint32_t stype = 0;               // jg_sel_type per slot, four bits each
+  uint32_t voff = 0, vtype = 0;     // the selected value that is open: where it began, its jg_sel_type
+  uint32_t ev = 0, eva = 0;         // this byte ends it (1; 2: as STRING_RAW) in front of eva
+  uint32_t soff[JG_MAX_SELECT] = {}, slen[JG_MAX_SELECT] = {};
+};
+struct ExtractSelect : Extract, SelState {};
+
+// The scan's compile-time modes: the verdict alone, with the jg_claims record,
+// and with the record and the caller's selected members (jg_selected)
+constexpr int kVerdict = 0, kExtract = 1, kSelect = 2;
+
+template <int M>
+struct ScanT : std::conditional_t<M == kSelect, ExtractSelect, std::conditional_t<M == kExtract, Extract, NoExtract>> {
   uint32_t st = ST_START;
   uint32_t depth = 0, stk = 0;      // open containers; bit d: container d+1 is an object
   uint32_t field = F_NONE;          // the top-level member whose value comes next
@@ -130,33 +194,69 @@ struct ScanT : std::conditional_t<X, Extract, NoExtract> {
   uint32_t aud_found = 0;
   int64_t exp = 0, nbf = 0, iat = 0;
 };
-using Scan = ScanT<false>;
+using Scan = ScanT<kVerdict>;
 
 JG_CL_HD bool is_ws(uint32_t c) { return c == 0x20u || c == 0x09u || c == 0x0au || c == 0x0du; }
 JG_CL_HD bool is_digit(uint32_t c) { return c - 0x30u < 10u; }
 
-template <bool X>
-JG_CL_HD void end_value(ScanT<X>& s) { s.st = s.depth == 0 ? (uint32_t)ST_DONE : (uint32_t)ST_AFTER; }
+// claims_select: the value of the selected depth-1 member (slot ksel - 1) begins
+// at decoded position `off` with jg_sel_type `type` (one such value is open at
+// a time: two scalars) ...
+template <int M>
+JG_CL_HD void sel_begin(ScanT<M>& s, uint32_t off, uint32_t type) {
+  if (s.depth != 1u || !s.ksel) return;
+  s.voff = off;
+  s.vtype = type;
+}
+// ... and ends in front of `end`.  raw: a string with a byte >= 0x80, whose span
+// takes the quotes in (JG_SEL_STRING_RAW)
+template <int M>
+JG_CL_HD void sel_end(ScanT<M>& s, uint32_t end, uint32_t raw) {
+  if (s.depth != 1u || !s.ksel) return;
+  s.ev = 1u + raw;
+  s.eva = end;
+}
+// A byte ends at most one value, so step() only notes the end and the slot is
+// latched here, in one place, once per byte, with values that do not depend on
+// the slot: latching at each place a value can begin or end costs the kernel 50
+// registers more.  The last member of a name wins: its end overwrites the slot.
+template <int M>
+JG_CL_HD void sel_commit(ScanT<M>& s) {
+  if (!s.ev) return;
+  const uint32_t raw = s.ev - 1u, sh = 4u * (s.ksel - 1u);
+  const uint32_t off = s.voff - raw, len = s.eva + raw - off;
+  s.stype = (s.stype & ~(0xfu << sh)) | ((s.vtype + raw) << sh);    // STRING + 1 = STRING_RAW
+  for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
+    const bool hit = s.ksel == k + 1u;
+    s.soff[k] = hit ? off : s.soff[k];
+    s.slen[k] = hit ? len : s.slen[k];
+  }
+  s.ev = 0;
+}
 
-template <bool X>
-JG_CL_HD void push(ScanT<X>& s, uint32_t is_obj) {
+template <int M>
+JG_CL_HD void end_value(ScanT<M>& s) { s.st = s.depth == 0 ? (uint32_t)ST_DONE : (uint32_t)ST_AFTER; }
+
+template <int M>
+JG_CL_HD void push(ScanT<M>& s, uint32_t is_obj) {
   if (s.depth >= 32u) { s.bad = 1; return; }
   s.stk = (s.stk & ~(1u << s.depth)) | (is_obj << s.depth);
   ++s.depth;
 }
 
-template <bool X>
-JG_CL_HD void pop(ScanT<X>& s, uint32_t is_obj) {
+template <int M>
+JG_CL_HD void pop(ScanT<M>& s, uint32_t is_obj) {
   if (((s.stk >> (s.depth - 1u)) & 1u) != is_obj) { s.bad = 1; return; }
   --s.depth;
-  if constexpr (X) s.aud_len = s.depth == 1u && s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud's ]
+  if constexpr (M >= kExtract) s.aud_len = s.depth == 1u && s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud's ]
   if (s.depth == 1u) s.aud_arr = 0;
+  if constexpr (M == kSelect) sel_end(s, s.dpos + 1u, 0u);        // the selected member's ] or }
   end_value(s);
 }
 
 // the first byte of a value
-template <bool X>
-JG_CL_HD void begin_value(ScanT<X>& s, uint32_t c, const Expect& E) {
+template <int M>
+JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const Expect& E) {
   const uint32_t f = s.depth == 1u ? s.field : (uint32_t)F_NONE;
   const uint32_t elem = s.depth == 2u && s.aud_arr;        // an element of aud's array
   const uint32_t is_str3 = f - F_ISS < 3u, is_date = f - F_EXP < 3u;
@@ -169,7 +269,7 @@ JG_CL_HD void begin_value(ScanT<X>& s, uint32_t c, const Expect& E) {
     s.cmpf = elem ? (uint32_t)F_AUD : f;
     s.cand = is_str3 ? (E.len[f - 1u] ? 1u << (f - 1u) : 0u)
            : (f == F_AUD || elem) ? ((1u << E.naud) - 1u) << 3 : 0u;
-    if constexpr (X) {
+    if constexpr (M >= kExtract) {
       const uint32_t in = s.dpos + 1u;                 // the first byte between the quotes
       s.iss_off = f == F_ISS ? in : s.iss_off;
       s.sub_off = f == F_SUB ? in : s.sub_off;
@@ -178,11 +278,16 @@ JG_CL_HD void begin_value(ScanT<X>& s, uint32_t c, const Expect& E) {
       s.aud_n = f == F_AUD ? 1u : s.aud_n + elem;
       s.present |= (is_str3 || f == F_AUD) ? 1u << f : 0u;
     }
+    if constexpr (M == kSelect) {
+      s.hi = 0;
+      sel_begin(s, s.dpos + 1u, (uint32_t)JG_SEL_STRING);
+    }
   } else if (c == '{' || c == '[') {
     const uint32_t arr = c == '[';
+    if constexpr (M == kSelect) sel_begin(s, s.dpos, arr ? (uint32_t)JG_SEL_ARRAY : (uint32_t)JG_SEL_OBJECT);
     if (arr && f == F_AUD) {
       s.aud_arr = 1;
-      if constexpr (X) {
+      if constexpr (M >= kExtract) {
         s.aud_off = s.dpos;
         s.present |= 1u << F_AUD;
       }
@@ -192,10 +297,13 @@ JG_CL_HD void begin_value(ScanT<X>& s, uint32_t c, const Expect& E) {
   } else if (c == 't' || c == 'f' || c == 'n') {
     // null: skipped for iss/sub/jti, absent for a date; any literal elsewhere
     if ((f != F_NONE || elem) && !(c == 'n' && (is_str3 || is_date))) s.bad = 1;
+    if constexpr (M == kSelect)
+      sel_begin(s, s.dpos, c == 't' ? (uint32_t)JG_SEL_TRUE : c == 'f' ? (uint32_t)JG_SEL_FALSE : (uint32_t)JG_SEL_NULL);
     s.lit = c == 't' ? 0x657572u : c == 'f' ? 0x65736c61u : 0x6c6c75u;   // "rue" / "alse" / "ull"
     s.st = ST_LIT;
   } else if (c == '-' || is_digit(c)) {
     if (!is_date && (f != F_NONE || elem)) s.bad = 1;
+    if constexpr (M == kSelect) sel_begin(s, s.dpos, (uint32_t)JG_SEL_NUMBER);
     s.isdate = is_date;
     s.nlen = 1;
     s.neg = c == '-';
@@ -208,8 +316,8 @@ JG_CL_HD void begin_value(ScanT<X>& s, uint32_t c, const Expect& E) {
 }
 
 // a number ended in front of the current byte
-template <bool X>
-JG_CL_HD void end_number(ScanT<X>& s) {
+template <int M>
+JG_CL_HD void end_number(ScanT<M>& s) {
   if (s.isdate) {
     // -?(0|[1-9][0-9]{0,14}), not -0: exact in float64 and far from any wrap
     if (s.st != ST_NUM_ZERO && s.st != ST_NUM_INT) s.bad = 1;
@@ -219,13 +327,15 @@ JG_CL_HD void end_number(ScanT<X>& s) {
     s.exp = s.field == F_EXP ? v : s.exp;
     s.nbf = s.field == F_NBF ? v : s.nbf;
     s.iat = s.field == F_IAT ? v : s.iat;
-    if constexpr (X) s.present |= 1u << s.field;
+    if constexpr (M >= kExtract) s.present |= 1u << s.field;
   }
+  if constexpr (M == kSelect) sel_end(s, s.dpos, 0u);              // dpos: the byte after the literal
   s.st = ST_AFTER;
 }
 
-template <bool X>
-JG_CL_HD void step(ScanT<X>& s, uint32_t c, const Expect& E) {
+template <int M>
+JG_CL_HD void step(ScanT<M>& s, uint32_t c, const Expect& E, const Select* S) {
+  (void)S;
   if (s.st >= ST_NUM_MINUS && s.st <= ST_NUM_FRAC) {
     const uint32_t d = is_digit(c);
     uint32_t nx = ST_AFTER;                           // ST_AFTER: the number ends here
@@ -257,6 +367,15 @@ JG_CL_HD void step(ScanT<X>& s, uint32_t c, const Expect& E) {
               if ((s.seen >> s.field) & 1u) s.bad = 1;          // named twice: Go takes the last in sorted order
               s.seen |= 1u << s.field;
             }
+            if constexpr (M == kSelect) {                       // the name this key is, exactly, or none
+              uint32_t m = s.kcand, slot = 0;
+              while (m) {
+                const uint32_t k = (uint32_t)__builtin_ctz(m);
+                m &= m - 1u;
+                slot = S->len[k] == s.klen ? k + 1u : slot;
+              }
+              s.ksel = slot;
+            }
           }
         } else {
           uint32_t m = s.cand, hit = 0;
@@ -267,18 +386,28 @@ JG_CL_HD void step(ScanT<X>& s, uint32_t c, const Expect& E) {
           }
           if (s.cmpf == F_AUD) s.aud_found |= hit;
           else if (s.cmpf != F_NONE) s.str_ok |= hit << s.cmpf;
-          if constexpr (X) {
+          if constexpr (M >= kExtract) {
             s.iss_len = s.cmpf == F_ISS ? s.pos : s.iss_len;
             s.sub_len = s.cmpf == F_SUB ? s.pos : s.sub_len;
             s.jti_len = s.cmpf == F_JTI ? s.pos : s.jti_len;
             s.aud_len = s.cmpf == F_AUD && !s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud as one string
           }
+          if constexpr (M == kSelect) sel_end(s, s.dpos, s.hi);
           end_value(s);
         }
       } else {
         if (c < 0x20u || c == '\\') s.bad = 1;
         if (c >= 0x80u && s.ascii_only) s.bad = 1;
+        if constexpr (M == kSelect) s.hi |= c >= 0x80u;
         if (s.is_key) {
+          if constexpr (M == kSelect) {                         // names still equal to the key so far
+            uint32_t m = s.kcand;
+            while (m) {
+              const uint32_t k = (uint32_t)__builtin_ctz(m);
+              m &= m - 1u;
+              if (!(s.klen < S->len[k] && S->bytes[S->off[k] + s.klen] == c)) s.kcand &= ~(1u << k);
+            }
+          }
           if (s.klen < 3u) s.kw = (s.kw << 8) | (c - 0x61u < 26u ? c - 0x20u : c);
           ++s.klen;
         }
@@ -294,7 +423,10 @@ JG_CL_HD void step(ScanT<X>& s, uint32_t c, const Expect& E) {
     case ST_LIT:
       if (c != (s.lit & 0xffu)) s.bad = 1;
       s.lit >>= 8;
-      if (s.lit == 0) end_value(s);
+      if (s.lit == 0) {
+        if constexpr (M == kSelect) sel_end(s, s.dpos + 1u, 0u);
+        end_value(s);
+      }
       break;
     case ST_START:
       if (c == '{') { push(s, 1u); s.st = ST_OBJ_FIRST; }
@@ -316,6 +448,7 @@ JG_CL_HD void step(ScanT<X>& s, uint32_t c, const Expect& E) {
         s.klen = 0;
         s.kw = 0;
         s.cand = 0;
+        if constexpr (M == kSelect) s.kcand = s.depth == 1u ? (1u << S->n) - 1u : 0u;
       } else if (c == '}' && s.st == ST_OBJ_FIRST) {
         pop(s, 1u);
       } else if (!is_ws(c)) {
@@ -356,8 +489,8 @@ JG_CL_HD uint32_t sextet(uint32_t c) {
 }
 
 // jwt/jwt.go:117-199 on the scanned fields, in Validate's order
-template <bool X>
-JG_CL_HD uint8_t verdict(const ScanT<X>& s, const Expect& E) {
+template <int M>
+JG_CL_HD uint8_t verdict(const ScanT<M>& s, const Expect& E) {
   int64_t iat = s.iat, exp = s.exp, nbf = s.nbf;
   if (iat == 0 && exp == 0 && nbf == 0) return JG_CL_NO_TIME;
   if (exp == 0) exp = (nbf > iat ? nbf : iat) + E.exp_leeway_s;
@@ -377,11 +510,13 @@ JG_CL_HD uint8_t verdict(const ScanT<X>& s, const Expect& E) {
 // The scan of one segment: claims_decide's code and, with X, the record.  The
 // state is a local of this function (handing it in by reference costs the
 // verdict-only kernel a third of its registers again).
-template <bool X, class Src>
-JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const Expect& E, jg_claims* out) {
-  if constexpr (X) *out = jg_claims{};                 // JG_CL_HOST: every byte zero
+template <int M, class Src>
+JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const Expect& E, jg_claims* out, const Select* S = nullptr,
+                              jg_selected* sel = nullptr) {
+  if constexpr (M >= kExtract) *out = jg_claims{};                 // JG_CL_HOST: every byte zero
+  if constexpr (M == kSelect) *sel = jg_selected{};
   if ((len & 3u) == 1u) return JG_CL_HOST;
-  ScanT<X> s;
+  ScanT<M> s;
   const uint32_t groups = (len + 3u) >> 2;
   for (uint32_t g = 0; g < groups && !s.bad; ++g) {
     const uint32_t w = src.word(g);
@@ -394,13 +529,14 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const Expect& E, jg_claims
     // Go's strict decoding: the bits the last group does not use are zero
     if (nb < 3u && (trip & (nb == 1u ? 0xffffu : 0xffu))) return JG_CL_HOST;
     for (uint32_t k = 0; k < nb; ++k) {
-      if constexpr (X) s.dpos = 3u * g + k;
-      step(s, (trip >> 16) & 0xffu, E);
+      if constexpr (M >= kExtract) s.dpos = 3u * g + k;
+      step(s, (trip >> 16) & 0xffu, E, S);
+      if constexpr (M == kSelect) sel_commit(s);
       trip <<= 8;
     }
   }
   if (s.bad || s.st != ST_DONE) return JG_CL_HOST;
-  if constexpr (X) {
+  if constexpr (M >= kExtract) {
     out->exp = s.exp;
     out->nbf = s.nbf;
     out->iat = s.iat;
@@ -415,12 +551,19 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const Expect& E, jg_claims
     out->aud_n = s.aud_n;
     out->present = s.present;
   }
+  if constexpr (M == kSelect) {
+    for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
+      sel->off[k] = s.soff[k];
+      sel->len[k] = s.slen[k];
+      sel->type[k] = (uint8_t)((s.stype >> (4u * k)) & 0xfu);
+    }
+  }
   return verdict(s, E);
 }
 
 template <class Src>
 JG_CL_HD uint8_t claims_decide(Src& src, uint32_t len, const Expect& E) {
-  return scan_segment<false>(src, len, E, nullptr);
+  return scan_segment<kVerdict>(src, len, E, nullptr);
 }
 
 // claims_decide's code for the same input, always, and the registered claims
@@ -429,7 +572,17 @@ JG_CL_HD uint8_t claims_decide(Src& src, uint32_t len, const Expect& E) {
 // registered value with an escape or a byte >= 0x80, or named twice, is HOST.
 template <class Src>
 JG_CL_HD uint8_t claims_extract(Src& src, uint32_t len, const Expect& E, jg_claims* out) {
-  return scan_segment<true>(src, len, E, out);
+  return scan_segment<kExtract>(src, len, E, out);
+}
+
+// claims_extract's code and record for the same input, always, and the
+// top-level members the caller named (include/jg.h jg_selected): slot k
+// describes the last depth-1 member whose key is name k byte for byte.  Filled
+// for every code other than JG_CL_HOST, all zero for JG_CL_HOST.
+template <class Src>
+JG_CL_HD uint8_t claims_select(Src& src, uint32_t len, const Expect& E, const Select& S, jg_claims* out,
+                               jg_selected* sel) {
+  return scan_segment<kSelect>(src, len, E, out, &S, sel);
 }
 
 }  // namespace jgclaims
@@ -442,4 +595,8 @@ void launch_claims_scan(const uint8_t* arena, const jg_cjob* jobs, int64_t n, co
 // ... and vals_out[i] = its registered claims (k_claims_extract)
 void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
                            uint8_t* code_out, jg_claims* vals_out, hipStream_t s);
+// ... and sel_out[i] = the members `select` (a device jgclaims::Select) names (k_claims_select)
+void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
+                          const jgclaims::Select* select, uint8_t* code_out, jg_claims* vals_out,
+                          jg_selected* sel_out, hipStream_t s);
 #endif

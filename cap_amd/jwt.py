@@ -15,6 +15,8 @@ returns become `(value, err)` tuples with `err` a str or None.
     Validator.Validate       jwt/jwt.go:95           Validator.Validate (+ ValidateBatch, north star)
     (verdict only)                                   Validator.CheckBatch / CheckBlob: Validate's error per
                                                      token, registered claims scanned on the GPU, no claims map
+    (verdict + named claims)                         Validator.RegisteredBatch / SelectBatch (+ Blob forms):
+                                                     jwt.Claims and caller-named claims from the same scan
     jwt.Expected             jwt/jwt.go:38           Expected
     jwt.SupportedSigningAlgorithm jwt/algs.go:38     SupportedSigningAlgorithm
 
@@ -212,6 +214,37 @@ class Validator:
         [n + 1] into the elements, element_offsets into data, data).  The rows of a
         rejected token are empty.  `stats` as in CheckBatch."""
         cols, scanned, host = self._impl.registered_blob(blob, (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
+    def SelectBatch(self, tokens: Sequence, names: Sequence[str], expected: Expected = None, stats: dict = None):
+        """RegisteredBatch plus top-level claims outside the registered seven, by name
+        (scope, roles, tenant, nonce, azp, auth_time, ...): [(claims or None, values or
+        None, err or None)], err == Validate(tokens[i], expected)[1] and claims as in
+        RegisteredBatch.  values is a dict name -> Python value holding only the names
+        the token's claims map has: exactly ValidateBatch's entries under those keys
+        (case-sensitive; null is None).  The GPU scan latches where each named value
+        lies; no claims map is built for a token the scan decides.  A name list the
+        scan does not take (more than 8 distinct names, a name that is empty, over 64
+        bytes, or not printable ASCII without quote and backslash) still answers,
+        from the host path.  A name with a NUL raises ValueError.  `stats` as in
+        CheckBatch."""
+        rows, scanned, host = self._impl.select_batch(list(tokens), list(names), (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return rows
+
+    def SelectBlob(self, blob: bytes, names: Sequence[str], expected: Expected = None, stats: dict = None) -> dict:
+        """SelectBatch's throughput form: newline-separated tokens -> columns.
+        RegisteredBlob's dict plus "sel": one dict per name with "type" (n bytes of
+        jg_sel_type: 0 absent, 1 string, 2 string with non-ASCII bytes, 3 number, 4 true,
+        5 false, 6 null, 7 array, 8 object; a token the host path decided reports 1
+        for any string), "num" (n little-endian float64: a number's value, else 0),
+        "text_off" (n + 1 little-endian uint32) and "text": a string's UTF-8 bytes,
+        an array's or object's JSON as Go's json.Marshal writes it, empty otherwise.
+        The rows of a rejected token are empty.  `stats` as in CheckBatch."""
+        cols, scanned, host = self._impl.select_blob(blob, list(names), (expected or Expected())._native())
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return cols

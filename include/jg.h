@@ -116,13 +116,16 @@ int jg_keys_wait_tables(jg_ctx* ctx);
  * RSA and invalid keys): widths[0..min(n, cap)).  Returns n, the key count. */
 int jg_keys_table_widths(jg_ctx* ctx, int* widths, int cap);
 
-/* Test / A-B hook: small submissions (at most 64 jobs, every job ECDSA or
- * rejected) run as one launch per (curve, key-table width) that does the whole
- * verification per token -- enable 1: on (the default), 0: off (they take the
- * batch chain: arena DMA, plan fill, prep, scalar, point, exact, scatter),
- * -1: unchanged.  Verdicts are identical either way.  Applies to later
- * submissions.  *launches (may be NULL) receives the number of such one-launch
- * verifications this context has enqueued.  Returns 0 or -1. */
+/* Test / A-B hook: small submissions (at most 64 jobs, every job rejected or of
+ * one of the one-launch classes: ECDSA on P-256 / P-384 / P-521, EdDSA, or
+ * RSA-2048 with PKCS#1 v1.5 -- RS256 / RS384 / RS512) run as one launch per
+ * (class, key-table width) that does the whole verification per token --
+ * enable 1: on (the default), 0: off (they take the batch chain: arena DMA,
+ * plan fill, prep, scalar, point, exact, scatter), -1: unchanged.  Verdicts are
+ * identical either way.  Applies to later submissions.  *launches (may be
+ * NULL) receives the number of such launches this context has enqueued: the
+ * counter counts launches, one per (class, width) group of a submission, not
+ * tokens.  Returns 0 or -1. */
 int jg_debug_small_path(jg_ctx* ctx, int enable, uint64_t* launches);
 
 /* Test hook: the n-th device allocation of later key loads (counting from 1)
@@ -388,6 +391,66 @@ typedef struct jg_claims {
 int jg_claims_extract(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                       const jg_cjob* jobs, size_t njobs, const jg_expect* expect,
                       uint8_t* code_out, jg_claims* vals_out);
+
+/* ---- the scan that also returns claims the caller names ----
+ * jg_claims_extract for callers that read a claim outside the registered seven
+ * after the verdict (scope, roles, tenant, email; the nonce, azp and auth_time
+ * of oidc/provider.go:445-506): the same jobs, the same `expect`, and
+ * code_out[i] and vals_out[i] are jg_claims_extract's for the same input, byte
+ * for byte, always -- selecting never changes a decision.  `select` names up to
+ * JG_MAX_SELECT claims, back to back in `names`, and sel_out[i] describes them:
+ *  - slot k is the top-level member whose key equals name k exactly, byte for
+ *    byte (case-sensitive: the claims map is a Go map[string]interface{}, not
+ *    the case-folding jwt.Claims struct).  A key at depth >= 2 never matches.
+ *    Where a name occurs more than once, the last occurrence wins, as in Go's
+ *    map decode.  The scan's rules already leave every payload whose keys could
+ *    differ from their bytes to the host (no backslash anywhere, no byte >= 0x80
+ *    in a top-level key), so no code depends on `select`.  A name may equal a
+ *    registered one ("sub"): it is matched exactly in its slot and, unchanged
+ *    and in any casing, by the registered logic;
+ *  - JG_SEL_ABSENT: no such member; off = len = 0;
+ *  - JG_SEL_STRING: a string whose bytes are all < 0x80; the span is the
+ *    contents between the quotes, as for iss ("" has len 0 and off = the
+ *    position after the opening quote);
+ *  - JG_SEL_STRING_RAW: a string that holds a byte >= 0x80; the span runs from
+ *    the opening quote through the closing quote, for the caller's JSON parser
+ *    (Go replaces invalid UTF-8 with U+FFFD);
+ *  - JG_SEL_NUMBER: the literal's text (at most 17 bytes, no exponent: the
+ *    scan's rule);
+ *  - JG_SEL_TRUE / FALSE / NULL: the literal's span (a member named with null
+ *    is NULL, not ABSENT: the map holds the key with nil);
+ *  - JG_SEL_ARRAY / OBJECT: from the opening bracket through its matching
+ *    closing bracket.
+ * Spans are byte spans [off, off + len) of the DECODED payload, as jg_claims'.
+ * For JG_CL_HOST all 80 bytes of the record are zero, as the jg_claims record
+ * is; for every other code, failure codes included, it is filled.  With
+ * select->n == 0 every slot is ABSENT.
+ * Everything else is jg_claims_extract's: blocking, on the context's first
+ * device on the same stream of its own and under the same lock (selects,
+ * extracts and scans of one context run one after the other, none waits for nor
+ * delays a jg_submit), device buffers kept between calls, 0 / -1 / -2 as there,
+ * njobs == 0 returns 0 without touching the buffers.  Also -1: select->n over
+ * JG_MAX_SELECT; a name of length 0 or over JG_SELECT_NAME_MAX; a name byte
+ * outside 0x20..0x7e or equal to " or \; two equal names; select, sel_out or
+ * vals_out NULL with njobs > 0. */
+#define JG_MAX_SELECT 8
+#define JG_SELECT_NAME_MAX 64
+typedef struct jg_select {          /* the caller's claim names, back to back in `names` */
+  const uint8_t* names;
+  uint32_t n;                       /* 0..JG_MAX_SELECT */
+  uint32_t name_len[JG_MAX_SELECT];
+} jg_select;
+enum jg_sel_type { JG_SEL_ABSENT = 0, JG_SEL_STRING = 1, JG_SEL_STRING_RAW = 2, JG_SEL_NUMBER = 3,
+                   JG_SEL_TRUE = 4, JG_SEL_FALSE = 5, JG_SEL_NULL = 6, JG_SEL_ARRAY = 7, JG_SEL_OBJECT = 8 };
+typedef struct jg_selected {        /* 80 bytes: five 16-byte stores */
+  uint32_t off[JG_MAX_SELECT];      /* byte span in the DECODED payload, as jg_claims' spans */
+  uint32_t len[JG_MAX_SELECT];
+  uint8_t  type[JG_MAX_SELECT];     /* jg_sel_type */
+  uint8_t  pad_[8];                 /* zero */
+} jg_selected;
+int jg_claims_select(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                     const jg_cjob* jobs, size_t njobs, const jg_expect* expect, const jg_select* select,
+                     uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out);
 
 /* Library build information (gfx target, version). */
 const char* jg_version(void);

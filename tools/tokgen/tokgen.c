@@ -7,7 +7,7 @@
  *
  * Token i uses key i % nkeys; header {"alg":ALG,"kid":"kid-KK","typ":"JWT"},
  * payload shaped like cap's testJWTClaims (jwt/keyset_test.go:666-677) with
- * jti = i.  One token per line.  PS* use salt length = hash length (go-jose).
+ * jti = i (TOKGEN_PAD / TOKGEN_EXTRA add members).  One token per line.  PS* use salt length = hash length (go-jose).
  * RS*, ES* and EdDSA tokens are the same bytes on every run (ES* nonces are
  * derived, see es_sign); PS* salts are random.
  */
@@ -109,9 +109,14 @@ static void* worker(void* arg) {
   const size_t padn = pe ? (size_t)atol(pe) : 0;
   const char* salt = getenv("TOKGEN_NONCE_SALT");
   if (!salt) salt = "";
+  /* TOKGEN_EXTRA=text: further members, written as they are in front of "sub"
+   * (e.g. "roles":["admin"],"scope":"read write", -- with the trailing comma) */
+  const char* extra = getenv("TOKGEN_EXTRA");
+  if (!extra) extra = "";
+  const size_t cap = 512 + padn + strlen(extra);
   char hdr[256], hb[512], sb[1500];
-  char* pay = malloc(512 + padn);
-  char* pb = malloc(2 * (512 + padn) + 8);
+  char* pay = malloc(cap);
+  char* pb = malloc(2 * cap + 8);
   char* padv = malloc(padn + 1);
   memset(padv, 'x', padn);
   padv[padn] = 0;
@@ -121,14 +126,15 @@ static void* worker(void* arg) {
     const int k = (int)(i % j->nkeys);
     snprintf(hdr, sizeof hdr, "{\"alg\":\"%s\",\"kid\":\"kid-%02d\",\"typ\":\"JWT\"}", j->alg, j->kid_base + k);
     if (padn)
-      snprintf(pay, 512 + padn,
+      snprintf(pay, cap,
                "{\"aud\":[\"www.example.com\"],\"exp\":1611699944,\"iat\":1611699344,"
                "\"iss\":\"https://example.com/\",\"jti\":\"%ld\",\"nbf\":1611699344,\"pad\":\"%s\","
-               "\"sub\":\"alice@example.com\"}", i, padv);
+               "%s\"sub\":\"alice@example.com\"}", i, padv, extra);
     else
-      snprintf(pay, 512,
+      snprintf(pay, cap,
                "{\"aud\":[\"www.example.com\"],\"exp\":1611699944,\"iat\":1611699344,"
-               "\"iss\":\"https://example.com/\",\"jti\":\"%ld\",\"nbf\":1611699344,\"sub\":\"alice@example.com\"}", i);
+               "\"iss\":\"https://example.com/\",\"jti\":\"%ld\",\"nbf\":1611699344,%s\"sub\":\"alice@example.com\"}",
+               i, extra);
     size_t hl = b64url((const unsigned char*)hdr, strlen(hdr), hb);
     size_t pl = b64url((const unsigned char*)pay, strlen(pay), pb);
     char* si = malloc(hl + pl + 2);
