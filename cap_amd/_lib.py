@@ -24,7 +24,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_submit", "jg_wait", "jg_set_chunk", "jg_set_zero_copy", "jg_set_table_budget", "jg_keys_wait_tables",
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
-           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select"]
+           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each"]
 
 
 class JgKey(ctypes.Structure):
@@ -42,6 +42,7 @@ class JgTok(ctypes.Structure):
 assert ctypes.sizeof(JgTok) == 24
 
 MAX_AUD = 16                       # JG_MAX_AUD
+MAX_PROFILES, PROFILE_POOL_BYTES = 64, 8192      # JG_MAX_PROFILES, JG_PROFILE_POOL_BYTES
 # jg_claim_code
 CL_OK, CL_NO_TIME, CL_ISS, CL_SUB, CL_JTI, CL_AUD, CL_NBF, CL_EXP, CL_IAT, CL_HOST = range(10)
 # the string Validator.Validate gives for each code (jwt/jwt.go:117-199)
@@ -148,6 +149,8 @@ def lib():
         L.jg_claims_extract.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect), vp, vp]
         L.jg_claims_select.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
                                        ctypes.POINTER(JgSelect), vp, vp, vp]
+        L.jg_claims_each.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                     ctypes.c_uint32, ctypes.POINTER(JgSelect), vp, vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -429,6 +432,67 @@ class Context:
             raise JgError(f"jg_claims_select rc={rc}: {self.error()}")
         return (out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n]),
                 (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n]))
+
+    def claims_each(self, arena_bytes, jobs, expects, mode="scan", names=None, nexpect=None):
+        """jg_claims_each: the three scans with a profile per job.  `jobs`: (off,
+        len, profile) triples; `expects`: a list of dicts as claims_scan takes one;
+        mode "scan" -> codes, "extract" -> (codes, vals), "select" (with `names`)
+        -> (codes, vals, sels), as claims_scan / claims_extract / claims_select
+        return them.  The outputs are poisoned with 0xee before the call.
+        `nexpect` overrides the count passed to the ABI (for its argument checks)."""
+        n = len(jobs)
+        cj = (JgCJob * max(1, n))()
+        for i, (off, ln, prof) in enumerate(jobs):
+            cj[i].off, cj[i].len, cj[i].flags = off, ln, prof
+        es = (JgExpect * max(1, len(expects)))()
+        keep = []
+        for e, expect in zip(es, expects):
+            auds = [bytes(a) for a in expect.get("audiences", [])]
+            strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
+            blob = b"".join(strs + auds)
+            keep.append(ctypes.create_string_buffer(blob, max(1, len(blob))))
+            e.strs = ctypes.cast(keep[-1], ctypes.c_void_p)
+            e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
+            e.naud = len(auds)
+            for k, a in enumerate(auds[:MAX_AUD]):
+                e.aud_len[k] = len(a)
+            e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
+            e.skew_ns = int(expect["skew_ns"])
+            e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
+        if mode not in ("scan", "extract", "select"):
+            raise ValueError("mode: scan, extract or select")
+        sel = None
+        if names is not None:
+            names = [bytes(x) for x in names]
+            nblob = b"".join(names)
+            sel = JgSelect()
+            nkeep = ctypes.create_string_buffer(nblob, max(1, len(nblob)))
+            sel.names = ctypes.cast(nkeep, ctypes.c_void_p)
+            sel.n = len(names)
+            for k, x in enumerate(names[:MAX_SELECT]):
+                sel.name_len[k] = len(x)
+        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
+        vals = sels = None
+        if mode != "scan":
+            vals = (JgClaims * max(1, n))()
+            ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
+        if mode == "select":
+            sels = (JgSelected * max(1, n))()
+            ctypes.memset(sels, 0xee, ctypes.sizeof(sels))
+        buf = bytes(arena_bytes) or b"\0"
+        rc = lib().jg_claims_each(self.h, buf, len(arena_bytes), cj, n, es,
+                                  len(expects) if nexpect is None else nexpect,
+                                  ctypes.byref(sel) if sel is not None else None, out,
+                                  ctypes.cast(vals, ctypes.c_void_p) if vals is not None else None,
+                                  ctypes.cast(sels, ctypes.c_void_p) if sels is not None else None)
+        if rc != 0:
+            raise JgError(f"jg_claims_each rc={rc}: {self.error()}")
+        if mode == "scan":
+            return out.raw[:n]
+        v = (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n])
+        if mode == "extract":
+            return out.raw[:n], v
+        return out.raw[:n], v, (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n])
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

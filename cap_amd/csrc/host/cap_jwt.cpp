@@ -1983,23 +1983,21 @@ RegisteredClaims claims_of_record(std::string_view seg, const jg_claims& v) {
 // records, record(...) also receives token i's jg_selected and claims(...) the
 // verified claims map of the host-path token.
 constexpr int kCheckMode = 0, kRegisteredMode = 1, kSelectMode = 2;
-template <int M, class Put>
-void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected& expected, CheckStats* stats,
-                Put&& put, const jg_select* select = nullptr) {
-  constexpr bool X = M >= kRegisteredMode;
-  // a token that is not accepted carries no claims
-  auto reject = [&](size_t c, size_t i, std::string&& err) {
-    if constexpr (X) put.reject(c, i, std::move(err));
-    else put(i, false, std::move(err));
-  };
-  const int64_t now = expected.has_now ? expected.now_unix_ns : wall_now_ns();
-  const size_t n = tokens.size();
-  const int th = host_threads();
-  // the resolved Expected of the scan (include/jg.h jg_expect); one the ABI
-  // does not take (more than JG_MAX_AUD audiences, strings over
-  // JG_EXPECT_MAX_BYTES) leaves every token to the host path
+
+// One Expected as the scan takes it (include/jg.h jg_expect) and the clock its
+// tokens are held to.  scannable == false: one the ABI does not take (more than
+// JG_MAX_AUD audiences, strings over JG_EXPECT_MAX_BYTES); its tokens take the
+// host path.
+struct ScanProfile {
   jg_expect ex{};
-  std::string strs = expected.Issuer + expected.Subject + expected.ID;
+  std::string strs;
+  int64_t now = 0;
+  bool scannable = false;
+};
+void resolve_scan_profile(const Expected& expected, int64_t now, ScanProfile* P) {
+  jg_expect& ex = P->ex;
+  P->now = now;
+  P->strs = expected.Issuer + expected.Subject + expected.ID;
   ex.iss_len = (uint32_t)expected.Issuer.size();
   ex.sub_len = (uint32_t)expected.Subject.size();
   ex.jti_len = (uint32_t)expected.ID.size();
@@ -2008,22 +2006,66 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     ex.naud = (uint32_t)expected.Audiences.size();
     for (size_t k = 0; k < expected.Audiences.size(); ++k) {
       ex.aud_len[k] = (uint32_t)expected.Audiences[k].size();
-      strs += expected.Audiences[k];
+      P->strs += expected.Audiences[k];
     }
   }
-  scannable = scannable && strs.size() <= JG_EXPECT_MAX_BYTES;
-  if constexpr (M == kSelectMode) scannable = scannable && select != nullptr;
-  ex.strs = (const uint8_t*)strs.data();
-  {
-    int64_t s = now / kSecond, ns = now % kSecond;
-    if (ns < 0) { ns += kSecond; --s; }
-    ex.now_sec = s;
-    ex.now_nsec = (uint32_t)ns;
-  }
+  P->scannable = scannable && P->strs.size() <= JG_EXPECT_MAX_BYTES;
+  ex.strs = (const uint8_t*)P->strs.data();
+  int64_t s = now / kSecond, ns = now % kSecond;
+  if (ns < 0) { ns += kSecond; --s; }
+  ex.now_sec = s;
+  ex.now_nsec = (uint32_t)ns;
   const Leeways lw = resolve_leeways(expected);
   ex.skew_ns = lw.skew_ns;
   ex.exp_leeway_s = lw.exp_s;
   ex.nbf_leeway_s = lw.nbf_s;
+}
+
+// Each = false: one Expected (exps[0]) for every token, `which` unused -- the
+// six entries above.  Each = true (the *Each entries): token i is held to
+// exps[which[i]]: its clock, leeways, SigningAlgorithms and expected strings;
+// one signature submission and one scan call (jg_claims_each) for the batch.
+// Profiles get device slots in index order while they fit (scannable, fewer than
+// JG_MAX_PROFILES slots taken, JG_PROFILE_POOL_BYTES of strings in all); the
+// tokens of a profile without a slot are not scanned and take the host path,
+// as every token of an unscannable Expected does, so no result depends on the caps.
+template <int M, bool Each, class Put>
+void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected* exps, size_t nexp,
+                const uint32_t* which, CheckStats* stats, Put&& put, const jg_select* select = nullptr) {
+  constexpr bool X = M >= kRegisteredMode;
+  // a token that is not accepted carries no claims
+  auto reject = [&](size_t c, size_t i, std::string&& err) {
+    if constexpr (X) put.reject(c, i, std::move(err));
+    else put(i, false, std::move(err));
+  };
+  const size_t n = tokens.size();
+  const int th = host_threads();
+  // the profiles of the scan and slot[p], profile p's index in the call's
+  // table (exs) or -1; the wall clock is read once
+  std::vector<ScanProfile> prof(nexp);
+  std::vector<int32_t> slot(nexp, -1);
+  std::vector<jg_expect> exs;
+  {
+    bool have_wall = false;
+    int64_t wall = 0;
+    size_t pool = 0;
+    for (size_t p = 0; p < nexp; ++p) {
+      if (!exps[p].has_now && !have_wall) {
+        wall = wall_now_ns();
+        have_wall = true;
+      }
+      resolve_scan_profile(exps[p], exps[p].has_now ? exps[p].now_unix_ns : wall, &prof[p]);
+      bool fits = prof[p].scannable;
+      if constexpr (M == kSelectMode) fits = fits && select != nullptr;
+      if constexpr (Each)
+        fits = fits && exs.size() < JG_MAX_PROFILES && pool + prof[p].strs.size() <= JG_PROFILE_POOL_BYTES;
+      if (!fits) continue;
+      slot[p] = (int32_t)exs.size();
+      pool += prof[p].strs.size();
+      exs.push_back(prof[p].ex);
+    }
+  }
+  const bool scannable = !exs.empty();
   // code[i]: the device's verdict on token i's registered claims; JG_CL_HOST
   // also for a token that was never scanned.  Job i is token i's payload
   // segment inside the arena the signatures are verified from (a canonical
@@ -2055,6 +2097,11 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
         j.len = 0;
         j.flags = 0;
         if (!t.ncand || !t.lit) continue;
+        if constexpr (Each) {
+          const int32_t sl = slot[which[i]];
+          if (sl < 0) continue;                           // no slot: the host path
+          j.flags = (uint32_t)sl;
+        }
         const char* dot = (const char*)std::memchr(t.lit, '.', t.si_len);
         if (!dot) continue;
         const size_t d1 = (size_t)(dot - t.lit);
@@ -2064,7 +2111,12 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     });
     pt.lap("scan-jobs");
     try {
-      if constexpr (M == kSelectMode) eng.claims_select(V.arena, V.arena_len, jobs, n, &ex, select, code, recs, sels, true);
+      const jg_expect& ex = exs[0];
+      if constexpr (Each)
+        eng.claims_each(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(),
+                        M == kSelectMode ? select : nullptr, code, X ? recs : nullptr,
+                        M == kSelectMode ? sels : nullptr, true);
+      else if constexpr (M == kSelectMode) eng.claims_select(V.arena, V.arena_len, jobs, n, &ex, select, code, recs, sels, true);
       else if constexpr (X) eng.claims_extract(V.arena, V.arena_len, jobs, n, &ex, code, recs, true);
       else eng.claims_scan(V.arena, V.arena_len, jobs, n, &ex, code, true);
     } catch (const DeviceError& e) {
@@ -2081,10 +2133,14 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   PhaseTimer pt("check");
   const Chunks ch = make_chunks(n, th);
   std::vector<size_t> n_scan(ch.count(), 0), n_host(ch.count(), 0);
+  const Expected* const one = exps;                   // Each = false: the one Expected and its clock
+  const int64_t one_now = Each ? 0 : prof[0].now;
   run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
     size_t ns = 0, nh = 0;
     for (size_t i = lo; i < hi; ++i) {
       const Tok& t = V->toks[i];
+      const Expected& expected = Each ? exps[which[i]] : *one;
+      const int64_t now = Each ? prof[which[i]].now : one_now;
       if (!(t.parsed && !V->failed[i] && V->any[i])) {
         Result r;                                     // the key set's own error string; no claims are read
         ks_->finish(*V, i, r);
@@ -2151,7 +2207,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
 std::vector<CheckResult> Validator::CheckBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
                                                CheckStats* stats) {
   std::vector<CheckResult> out(tokens.size());
-  check_core<kCheckMode>(ks_, tokens, expected, stats, [&](size_t i, bool ok, std::string&& err) {
+  check_core<kCheckMode, false>(ks_, tokens, &expected, 1, nullptr, stats, [&](size_t i, bool ok, std::string&& err) {
     out[i].ok = ok;
     out[i].err = std::move(err);
   });
@@ -2275,7 +2331,7 @@ struct ColumnSink {
 std::vector<RegisteredResult> Validator::RegisteredBatch(const std::vector<std::string_view>& tokens,
                                                          const Expected& expected, CheckStats* stats) {
   std::vector<RegisteredResult> out(tokens.size());
-  check_core<kRegisteredMode>(ks_, tokens, expected, stats, RowSink{out});
+  check_core<kRegisteredMode, false>(ks_, tokens, &expected, 1, nullptr, stats, RowSink{out});
   return out;
 }
 
@@ -2283,7 +2339,7 @@ void Validator::RegisteredCols(const std::vector<std::string_view>& tokens, cons
                                const RegisteredColumns& out, CheckStats* stats) {
   const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
   ColumnSink sink(out, ch);
-  check_core<kRegisteredMode>(ks_, tokens, expected, stats, sink);
+  check_core<kRegisteredMode, false>(ks_, tokens, &expected, 1, nullptr, stats, sink);
   PhaseTimer pt("check");
   sink.finish();
   pt.lap("columns");
@@ -2454,7 +2510,7 @@ std::vector<SelectResult> Validator::SelectBatch(const std::vector<std::string_v
                                                  const std::vector<std::string>& names, CheckStats* stats) {
   const SelectNames N(names);
   std::vector<SelectResult> out(tokens.size());
-  check_core<kSelectMode>(ks_, tokens, expected, stats, SelectRowSink{out, names, N}, N.select());
+  check_core<kSelectMode, false>(ks_, tokens, &expected, 1, nullptr, stats, SelectRowSink{out, names, N}, N.select());
   return out;
 }
 
@@ -2464,7 +2520,7 @@ void Validator::SelectCols(const std::vector<std::string_view>& tokens, const Ex
   const SelectNames N(names);
   const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
   SelectColumnSink sink(out, names, N, ch);
-  check_core<kSelectMode>(ks_, tokens, expected, stats, sink, N.select());
+  check_core<kSelectMode, false>(ks_, tokens, &expected, 1, nullptr, stats, sink, N.select());
   PhaseTimer pt("check");
   sink.finish();
   pt.lap("columns");
@@ -2473,8 +2529,95 @@ void Validator::SelectCols(const std::vector<std::string_view>& tokens, const Ex
 std::vector<uint8_t> Validator::CheckVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
                                               CheckStats* stats) {
   std::vector<uint8_t> ok(tokens.size(), 0);
-  check_core<kCheckMode>(ks_, tokens, expected, stats, [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
+  check_core<kCheckMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
+                                [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
   return ok;
+}
+
+// ---- the same six with an Expected per token
+namespace {
+void each_args(const char* what, const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+               const std::vector<uint32_t>& which) {
+  if (which.size() != tokens.size())
+    throw std::invalid_argument(std::string("capjwt: ") + what + ": one profile index per token");
+  if (expected.empty() && !tokens.empty())
+    throw std::invalid_argument(std::string("capjwt: ") + what + ": no Expected");
+  for (size_t i = 0; i < which.size(); ++i)
+    if (which[i] >= expected.size())
+      throw std::invalid_argument(std::string("capjwt: ") + what + ": token " + std::to_string(i) +
+                                  " names profile " + std::to_string(which[i]) + " of " +
+                                  std::to_string(expected.size()));
+}
+}  // namespace
+
+std::vector<CheckResult> Validator::CheckBatchEach(const std::vector<std::string_view>& tokens,
+                                                   const std::vector<Expected>& expected,
+                                                   const std::vector<uint32_t>& which, CheckStats* stats) {
+  each_args("CheckBatchEach", tokens, expected, which);
+  std::vector<CheckResult> out(tokens.size());
+  check_core<kCheckMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                               [&](size_t i, bool ok, std::string&& err) {
+                                 out[i].ok = ok;
+                                 out[i].err = std::move(err);
+                               });
+  return out;
+}
+
+std::vector<uint8_t> Validator::CheckVerdictsEach(const std::vector<std::string_view>& tokens,
+                                                  const std::vector<Expected>& expected,
+                                                  const std::vector<uint32_t>& which, CheckStats* stats) {
+  each_args("CheckVerdictsEach", tokens, expected, which);
+  std::vector<uint8_t> ok(tokens.size(), 0);
+  check_core<kCheckMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                               [&](size_t i, bool good, std::string&&) { ok[i] = good ? 1 : 0; });
+  return ok;
+}
+
+std::vector<RegisteredResult> Validator::RegisteredBatchEach(const std::vector<std::string_view>& tokens,
+                                                             const std::vector<Expected>& expected,
+                                                             const std::vector<uint32_t>& which, CheckStats* stats) {
+  each_args("RegisteredBatchEach", tokens, expected, which);
+  std::vector<RegisteredResult> out(tokens.size());
+  check_core<kRegisteredMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats, RowSink{out});
+  return out;
+}
+
+void Validator::RegisteredColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                                   const std::vector<uint32_t>& which, const RegisteredColumns& out,
+                                   CheckStats* stats) {
+  each_args("RegisteredColsEach", tokens, expected, which);
+  const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
+  ColumnSink sink(out, ch);
+  check_core<kRegisteredMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats, sink);
+  PhaseTimer pt("check");
+  sink.finish();
+  pt.lap("columns");
+}
+
+std::vector<SelectResult> Validator::SelectBatchEach(const std::vector<std::string_view>& tokens,
+                                                     const std::vector<Expected>& expected,
+                                                     const std::vector<uint32_t>& which,
+                                                     const std::vector<std::string>& names, CheckStats* stats) {
+  each_args("SelectBatchEach", tokens, expected, which);
+  const SelectNames N(names);
+  std::vector<SelectResult> out(tokens.size());
+  check_core<kSelectMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                                SelectRowSink{out, names, N}, N.select());
+  return out;
+}
+
+void Validator::SelectColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                               const std::vector<uint32_t>& which, const std::vector<std::string>& names,
+                               const SelectColumns& out, CheckStats* stats) {
+  if (out.names.size() != names.size()) throw std::invalid_argument("capjwt: SelectColsEach: one column set per name");
+  each_args("SelectColsEach", tokens, expected, which);
+  const SelectNames N(names);
+  const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
+  SelectColumnSink sink(out, names, N, ch);
+  check_core<kSelectMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats, sink, N.select());
+  PhaseTimer pt("check");
+  sink.finish();
+  pt.lap("columns");
 }
 
 // ====================================================================== oidc hash claims
@@ -2538,6 +2681,25 @@ void Engine::claims_select(const uint8_t* arena, size_t arena_len, const void* j
   if (rc == -1)
     throw std::logic_error(std::string("capjwt: jg_claims_select rejected the host's jobs: ") + jg_last_error(ctx_));
   if (rc != 0) fail_device(std::string("capjwt: jg_claims_select: ") + jg_last_error(ctx_));
+}
+
+// ... and jg_claims_each (the *Each entries): the three scans with a profile per job
+extern "C" __attribute__((weak)) int jg_claims_each(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
+                                                    const jg_expect*, uint32_t, const jg_select*, uint8_t*, jg_claims*,
+                                                    jg_selected*);
+
+void Engine::claims_each(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                         uint32_t nexpect, const void* select, uint8_t* codes, void* vals, void* sels,
+                         bool inside_verify) {
+  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
+  if (!inside_verify) life.lock();
+  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
+  if (!jg_claims_each) fail_device("capjwt: jg_claims_each: not provided by the loaded verifier library");
+  const int rc = jg_claims_each(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                                (const jg_select*)select, codes, (jg_claims*)vals, (jg_selected*)sels);
+  if (rc == -1)
+    throw std::logic_error(std::string("capjwt: jg_claims_each rejected the host's jobs: ") + jg_last_error(ctx_));
+  if (rc != 0) fail_device(std::string("capjwt: jg_claims_each: ") + jg_last_error(ctx_));
 }
 
 namespace {

@@ -203,6 +203,12 @@ class Engine {
   // jg_select) names (jg_claims_select)
   void claims_select(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
                      const void* select, uint8_t* codes, void* vals, void* sels, bool inside_verify = false);
+  // The three scans with a profile per job (jg_claims_each): `expects` is
+  // nexpect jg_expect and a job's flags names its own; sels (with select and
+  // vals) asks for claims_select's outputs, else vals for claims_extract's
+  void claims_each(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                   uint32_t nexpect, const void* select, uint8_t* codes, void* vals, void* sels,
+                   bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -540,6 +546,36 @@ class Validator {
   // records (SelectBlob); out.names.size() == names.size()
   void SelectCols(const std::vector<std::string_view>& tokens, const Expected& expected,
                   const std::vector<std::string>& names, const SelectColumns& out, CheckStats* stats = nullptr);
+  // The six entries above with an Expected per token, as Validate takes its
+  // Expected per call: token i is held to expected[which[i]] -- its issuer,
+  // audiences, subject, ID, SigningAlgorithms, Now (a profile without one reads
+  // the wall clock, once per call) and leeways -- and its result is exactly what
+  // the entry above returns for tokens[i] alone with that Expected.  One
+  // signature submission and one scan (jg_claims_each) for the whole batch,
+  // where a caller had to split it by tenant.  The scan's table holds
+  // JG_MAX_PROFILES profiles and JG_PROFILE_POOL_BYTES of expected strings;
+  // tokens of a profile beyond that, or of one the scan does not take, go the
+  // host path, so results do not depend on the caps.  std::invalid_argument:
+  // which.size() != tokens.size(), a which[i] >= expected.size(), no Expected
+  // with tokens.
+  std::vector<CheckResult> CheckBatchEach(const std::vector<std::string_view>& tokens,
+                                          const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
+                                          CheckStats* stats = nullptr);
+  std::vector<uint8_t> CheckVerdictsEach(const std::vector<std::string_view>& tokens,
+                                         const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
+                                         CheckStats* stats = nullptr);
+  std::vector<RegisteredResult> RegisteredBatchEach(const std::vector<std::string_view>& tokens,
+                                                    const std::vector<Expected>& expected,
+                                                    const std::vector<uint32_t>& which, CheckStats* stats = nullptr);
+  void RegisteredColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                          const std::vector<uint32_t>& which, const RegisteredColumns& out,
+                          CheckStats* stats = nullptr);
+  std::vector<SelectResult> SelectBatchEach(const std::vector<std::string_view>& tokens,
+                                            const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
+                                            const std::vector<std::string>& names, CheckStats* stats = nullptr);
+  void SelectColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                      const std::vector<uint32_t>& which, const std::vector<std::string>& names,
+                      const SelectColumns& out, CheckStats* stats = nullptr);
  private:
   KeySet* ks_;
 };

@@ -234,6 +234,18 @@ py::dict key_dict(const PublicKey& k) {
   return d;
 }
 
+// the per-token profile indices of a *_blob_each call: any C-contiguous buffer of uint32
+std::vector<uint32_t> which_of(const py::buffer& b) {
+  const py::buffer_info info = b.request();
+  if (info.itemsize != 4 || (info.format != py::format_descriptor<uint32_t>::format() && info.format != "L" &&
+                             info.format != "=I" && info.format != "<I"))
+    throw py::value_error("which must be a buffer of uint32");
+  if (info.ndim != 1 || (info.size > 0 && info.strides[0] != 4))
+    throw py::value_error("which must be contiguous, one dimension");
+  const uint32_t* p = (const uint32_t*)info.ptr;
+  return std::vector<uint32_t>(p, p + info.size);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_capjwt_host, m) {
@@ -447,6 +459,183 @@ PYBIND11_MODULE(_capjwt_host, m) {
     std::shared_ptr<KeySet> ks;
     std::unique_ptr<Validator> v;
   };
+  // check_batch .. select_blob below, once for one Expected (e) and once for an
+  // Expected per token (es[w[i]]): the *_each bindings
+  struct Who {
+    const Expected* e;
+    const std::vector<Expected>* es;
+    const std::vector<uint32_t>* w;
+  };
+  auto py_check_batch = [](PyValidator& s, py::sequence toks, const Who& who) {
+    // verdict only: (list of error strings or None, tokens the device's
+    // claims scan decided, tokens that took the host claims path)
+    auto v = as_strings(toks);
+    std::vector<CheckResult> rs;
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      rs = who.es ? s.v->CheckBatchEach(views(v), *who.es, *who.w, &st) : s.v->CheckBatch(views(v), *who.e, &st);
+    }
+    py::list out(rs.size());
+    for (size_t i = 0; i < rs.size(); ++i) {
+      if (rs[i].ok) out[i] = py::none();
+      else out[i] = py::str(rs[i].err);
+    }
+    return py::make_tuple(out, st.scanned, st.host);
+  };
+  auto py_check_blob = [](PyValidator& s, py::bytes blob, const Who& who) {
+    // validate_blob's verdict-only twin: newline-separated tokens in,
+    // (accept bytes, scanned, host) out
+    char* bp = nullptr;
+    Py_ssize_t bn = 0;
+    if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+    std::string ok;
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+      auto t0 = std::chrono::steady_clock::now();
+      auto lap = [&](const char* what) {
+        if (!trace) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[capjwt] cblob %-12s %8.2f ms\n", what,
+                     std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+      };
+      auto toks = split_lines(bp, (size_t)bn);
+      lap("split");
+      const auto rs = who.es ? s.v->CheckVerdictsEach(toks, *who.es, *who.w, &st)
+                             : s.v->CheckVerdicts(toks, *who.e, &st);
+      lap("check");
+      ok.assign((const char*)rs.data(), rs.size());
+      lap("verdicts");
+    }
+    return py::make_tuple(py::bytes(ok), st.scanned, st.host);
+  };
+  auto py_registered_batch = [](PyValidator& s, py::sequence toks, const Who& who) {
+    // check_batch with jwt.Claims: ([(claims dict or None, error or None)], scanned, host)
+    auto v = as_strings(toks);
+    std::vector<RegisteredResult> rs;
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      rs = who.es ? s.v->RegisteredBatchEach(views(v), *who.es, *who.w, &st)
+                  : s.v->RegisteredBatch(views(v), *who.e, &st);
+    }
+    py::list out(rs.size());
+    for (size_t i = 0; i < rs.size(); ++i) {
+      if (!rs[i].ok) out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
+      else out[i] = py::make_tuple(claims_py(rs[i].claims), py::none());
+    }
+    return py::make_tuple(out, st.scanned, st.host);
+  };
+  auto py_registered_blob = [](PyValidator& s, py::bytes blob, const Who& who) {
+    // check_blob with the registered claims as columns: newline-separated
+    // tokens in, (dict of bytes, scanned, host) out -- no per-token object
+    char* bp = nullptr;
+    Py_ssize_t bn = 0;
+    if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+    const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+      if (!trace) return;
+      const auto t1 = std::chrono::steady_clock::now();
+      std::fprintf(stderr, "[capjwt] rblob %-12s %8.2f ms\n", what,
+                   std::chrono::duration<double, std::milli>(t1 - t0).count());
+      t0 = t1;
+    };
+    auto toks = split_lines(bp, (size_t)bn);
+    lap("split");
+    // the columns are bytes objects from the start
+    RegisteredBlobCols C(toks.size());
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      if (who.es) s.v->RegisteredColsEach(toks, *who.es, *who.w, C.R, &st);
+      else s.v->RegisteredCols(toks, *who.e, C.R, &st);
+    }
+    lap("registered");
+    return py::make_tuple(C.dict(), st.scanned, st.host);
+  };
+  auto py_select_batch = [](PyValidator& s, py::sequence toks, std::vector<std::string> names, const Who& who) {
+    // registered_batch with the claims `names` name:
+    // ([(claims dict or None, {name: value} or None, error or None)], scanned, host)
+    auto v = as_strings(toks);
+    std::vector<SelectResult> rs;
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      rs = who.es ? s.v->SelectBatchEach(views(v), *who.es, *who.w, names, &st)
+                  : s.v->SelectBatch(views(v), *who.e, names, &st);
+    }
+    py::list out(rs.size());
+    for (size_t i = 0; i < rs.size(); ++i) {
+      if (!rs[i].ok) {
+        out[i] = py::make_tuple(py::none(), py::none(), py::str(rs[i].err));
+        continue;
+      }
+      py::dict vals;
+      for (size_t k = 0; k < names.size(); ++k)
+        if (rs[i].values[k]) vals[py::str(names[k])] = to_py(*rs[i].values[k]);
+      out[i] = py::make_tuple(claims_py(rs[i].claims), vals, py::none());
+    }
+    return py::make_tuple(out, st.scanned, st.host);
+  };
+  auto py_select_blob = [](PyValidator& s, py::bytes blob, std::vector<std::string> names, const Who& who) {
+    // registered_blob with, per name, the value's type / number / text columns
+    char* bp = nullptr;
+    Py_ssize_t bn = 0;
+    if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+    const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+      if (!trace) return;
+      const auto t1 = std::chrono::steady_clock::now();
+      std::fprintf(stderr, "[capjwt] sblob %-12s %8.2f ms\n", what,
+                   std::chrono::duration<double, std::milli>(t1 - t0).count());
+      t0 = t1;
+    };
+    auto toks = split_lines(bp, (size_t)bn);
+    lap("split");
+    const size_t n = toks.size();
+    RegisteredBlobCols C(n);
+    std::vector<py::bytes> type(names.size()), num(names.size()), text_off(names.size()), text(names.size());
+    SelectColumns S;
+    S.reg = C.R;
+    S.names.resize(names.size());
+    for (size_t k = 0; k < names.size(); ++k) {
+      type[k] = fresh_bytes(n);
+      num[k] = fresh_bytes(8 * n);
+      text_off[k] = fresh_bytes(4 * (n + 1));
+      S.names[k].type = (uint8_t*)bytes_mem(type[k]);
+      S.names[k].num = (double*)bytes_mem(num[k]);
+      S.names[k].text_off = (uint32_t*)bytes_mem(text_off[k]);
+    }
+    S.alloc_text = [&](size_t k, size_t bytes) {
+      py::gil_scoped_acquire gil;
+      text[k] = fresh_bytes(bytes);
+      return bytes_mem(text[k]);
+    };
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      if (who.es) s.v->SelectColsEach(toks, *who.es, *who.w, names, S, &st);
+      else s.v->SelectCols(toks, *who.e, names, S, &st);
+    }
+    lap("select");
+    py::dict d = C.dict();
+    py::list sel;
+    for (size_t k = 0; k < names.size(); ++k) {
+      py::dict c;
+      c["type"] = type[k];
+      c["num"] = num[k];
+      c["text_off"] = text_off[k];
+      c["text"] = text[k];
+      sel.append(c);
+    }
+    d["sel"] = sel;
+    return py::make_tuple(d, st.scanned, st.host);
+  };
   py::class_<PyValidator>(m, "Validator")
       .def(py::init([](PyKeySet* ks) {
         if (!ks) throw py::value_error("keySet must not be nil");
@@ -504,170 +693,50 @@ PYBIND11_MODULE(_capjwt_host, m) {
         }
         return py::bytes(ok);
       })
-      .def("check_batch", [](PyValidator& s, py::sequence toks, const Expected& e) {
-        // verdict only: (list of error strings or None, tokens the device's
-        // claims scan decided, tokens that took the host claims path)
-        auto v = as_strings(toks);
-        std::vector<CheckResult> rs;
-        CheckStats st;
-        {
-          py::gil_scoped_release rel;
-          rs = s.v->CheckBatch(views(v), e, &st);
-        }
-        py::list out(rs.size());
-        for (size_t i = 0; i < rs.size(); ++i) {
-          if (rs[i].ok) out[i] = py::none();
-          else out[i] = py::str(rs[i].err);
-        }
-        return py::make_tuple(out, st.scanned, st.host);
+      .def("check_batch", [=](PyValidator& s, py::sequence toks, const Expected& e) {
+        return py_check_batch(s, toks, Who{&e, nullptr, nullptr});
       })
-      .def("check_blob", [](PyValidator& s, py::bytes blob, const Expected& e) {
-        // validate_blob's verdict-only twin: newline-separated tokens in,
-        // (accept bytes, scanned, host) out
-        char* bp = nullptr;
-        Py_ssize_t bn = 0;
-        if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
-        std::string ok;
-        CheckStats st;
-        {
-          py::gil_scoped_release rel;
-          const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
-          auto t0 = std::chrono::steady_clock::now();
-          auto lap = [&](const char* what) {
-            if (!trace) return;
-            const auto t1 = std::chrono::steady_clock::now();
-            std::fprintf(stderr, "[capjwt] cblob %-12s %8.2f ms\n", what,
-                         std::chrono::duration<double, std::milli>(t1 - t0).count());
-            t0 = t1;
-          };
-          auto toks = split_lines(bp, (size_t)bn);
-          lap("split");
-          const auto rs = s.v->CheckVerdicts(toks, e, &st);
-          lap("check");
-          ok.assign((const char*)rs.data(), rs.size());
-          lap("verdicts");
-        }
-        return py::make_tuple(py::bytes(ok), st.scanned, st.host);
+      .def("check_batch_each", [=](PyValidator& s, py::sequence toks,
+                                  const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
+        return py_check_batch(s, toks, Who{nullptr, &es, &which});
       })
-      .def("registered_batch", [](PyValidator& s, py::sequence toks, const Expected& e) {
-        // check_batch with jwt.Claims: ([(claims dict or None, error or None)], scanned, host)
-        auto v = as_strings(toks);
-        std::vector<RegisteredResult> rs;
-        CheckStats st;
-        {
-          py::gil_scoped_release rel;
-          rs = s.v->RegisteredBatch(views(v), e, &st);
-        }
-        py::list out(rs.size());
-        for (size_t i = 0; i < rs.size(); ++i) {
-          if (!rs[i].ok) out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
-          else out[i] = py::make_tuple(claims_py(rs[i].claims), py::none());
-        }
-        return py::make_tuple(out, st.scanned, st.host);
+      .def("check_blob", [=](PyValidator& s, py::bytes blob, const Expected& e) {
+        return py_check_blob(s, blob, Who{&e, nullptr, nullptr});
       })
-      .def("registered_blob", [](PyValidator& s, py::bytes blob, const Expected& e) {
-        // check_blob with the registered claims as columns: newline-separated
-        // tokens in, (dict of bytes, scanned, host) out -- no per-token object
-        char* bp = nullptr;
-        Py_ssize_t bn = 0;
-        if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
-        const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-          if (!trace) return;
-          const auto t1 = std::chrono::steady_clock::now();
-          std::fprintf(stderr, "[capjwt] rblob %-12s %8.2f ms\n", what,
-                       std::chrono::duration<double, std::milli>(t1 - t0).count());
-          t0 = t1;
-        };
-        auto toks = split_lines(bp, (size_t)bn);
-        lap("split");
-        // the columns are bytes objects from the start
-        RegisteredBlobCols C(toks.size());
-        CheckStats st;
-        {
-          py::gil_scoped_release rel;
-          s.v->RegisteredCols(toks, e, C.R, &st);
-        }
-        lap("registered");
-        return py::make_tuple(C.dict(), st.scanned, st.host);
+      .def("check_blob_each", [=](PyValidator& s, py::bytes blob,
+                                 const std::vector<Expected>& es, py::buffer which) {
+        const std::vector<uint32_t> w = which_of(which);
+        return py_check_blob(s, blob, Who{nullptr, &es, &w});
       })
-      .def("select_batch", [](PyValidator& s, py::sequence toks, std::vector<std::string> names, const Expected& e) {
-        // registered_batch with the claims `names` name:
-        // ([(claims dict or None, {name: value} or None, error or None)], scanned, host)
-        auto v = as_strings(toks);
-        std::vector<SelectResult> rs;
-        CheckStats st;
-        {
-          py::gil_scoped_release rel;
-          rs = s.v->SelectBatch(views(v), e, names, &st);
-        }
-        py::list out(rs.size());
-        for (size_t i = 0; i < rs.size(); ++i) {
-          if (!rs[i].ok) {
-            out[i] = py::make_tuple(py::none(), py::none(), py::str(rs[i].err));
-            continue;
-          }
-          py::dict vals;
-          for (size_t k = 0; k < names.size(); ++k)
-            if (rs[i].values[k]) vals[py::str(names[k])] = to_py(*rs[i].values[k]);
-          out[i] = py::make_tuple(claims_py(rs[i].claims), vals, py::none());
-        }
-        return py::make_tuple(out, st.scanned, st.host);
+      .def("registered_batch", [=](PyValidator& s, py::sequence toks, const Expected& e) {
+        return py_registered_batch(s, toks, Who{&e, nullptr, nullptr});
       })
-      .def("select_blob", [](PyValidator& s, py::bytes blob, std::vector<std::string> names, const Expected& e) {
-        // registered_blob with, per name, the value's type / number / text columns
-        char* bp = nullptr;
-        Py_ssize_t bn = 0;
-        if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
-        const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-          if (!trace) return;
-          const auto t1 = std::chrono::steady_clock::now();
-          std::fprintf(stderr, "[capjwt] sblob %-12s %8.2f ms\n", what,
-                       std::chrono::duration<double, std::milli>(t1 - t0).count());
-          t0 = t1;
-        };
-        auto toks = split_lines(bp, (size_t)bn);
-        lap("split");
-        const size_t n = toks.size();
-        RegisteredBlobCols C(n);
-        std::vector<py::bytes> type(names.size()), num(names.size()), text_off(names.size()), text(names.size());
-        SelectColumns S;
-        S.reg = C.R;
-        S.names.resize(names.size());
-        for (size_t k = 0; k < names.size(); ++k) {
-          type[k] = fresh_bytes(n);
-          num[k] = fresh_bytes(8 * n);
-          text_off[k] = fresh_bytes(4 * (n + 1));
-          S.names[k].type = (uint8_t*)bytes_mem(type[k]);
-          S.names[k].num = (double*)bytes_mem(num[k]);
-          S.names[k].text_off = (uint32_t*)bytes_mem(text_off[k]);
-        }
-        S.alloc_text = [&](size_t k, size_t bytes) {
-          py::gil_scoped_acquire gil;
-          text[k] = fresh_bytes(bytes);
-          return bytes_mem(text[k]);
-        };
-        CheckStats st;
-        {
-          py::gil_scoped_release rel;
-          s.v->SelectCols(toks, e, names, S, &st);
-        }
-        lap("select");
-        py::dict d = C.dict();
-        py::list sel;
-        for (size_t k = 0; k < names.size(); ++k) {
-          py::dict c;
-          c["type"] = type[k];
-          c["num"] = num[k];
-          c["text_off"] = text_off[k];
-          c["text"] = text[k];
-          sel.append(c);
-        }
-        d["sel"] = sel;
-        return py::make_tuple(d, st.scanned, st.host);
+      .def("registered_batch_each", [=](PyValidator& s, py::sequence toks,
+                                  const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
+        return py_registered_batch(s, toks, Who{nullptr, &es, &which});
+      })
+      .def("registered_blob", [=](PyValidator& s, py::bytes blob, const Expected& e) {
+        return py_registered_blob(s, blob, Who{&e, nullptr, nullptr});
+      })
+      .def("registered_blob_each", [=](PyValidator& s, py::bytes blob,
+                                 const std::vector<Expected>& es, py::buffer which) {
+        const std::vector<uint32_t> w = which_of(which);
+        return py_registered_blob(s, blob, Who{nullptr, &es, &w});
+      })
+      .def("select_batch", [=](PyValidator& s, py::sequence toks, std::vector<std::string> names, const Expected& e) {
+        return py_select_batch(s, toks, names, Who{&e, nullptr, nullptr});
+      })
+      .def("select_batch_each", [=](PyValidator& s, py::sequence toks, std::vector<std::string> names,
+                                  const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
+        return py_select_batch(s, toks, names, Who{nullptr, &es, &which});
+      })
+      .def("select_blob", [=](PyValidator& s, py::bytes blob, std::vector<std::string> names, const Expected& e) {
+        return py_select_blob(s, blob, names, Who{&e, nullptr, nullptr});
+      })
+      .def("select_blob_each", [=](PyValidator& s, py::bytes blob, std::vector<std::string> names,
+                                 const std::vector<Expected>& es, py::buffer which) {
+        const std::vector<uint32_t> w = which_of(which);
+        return py_select_blob(s, blob, names, Who{nullptr, &es, &w});
       })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {

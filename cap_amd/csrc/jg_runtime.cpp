@@ -717,6 +717,7 @@ struct Device {
   Grow cl_arena, cl_jobs, cl_out, cl_expect;
   Grow cl_vals;                     // jg_claims_extract's records
   Grow cl_select, cl_sel;           // jg_claims_select's resolved names and its records
+  Grow cl_profiles;                 // jg_claims_each's resolved table
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -3546,6 +3547,72 @@ int jg_claims_select(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(e.what());
+    return -2;
+  }
+}
+
+// The three scans with a profile per job: the same checks, stream, lock and kept
+// buffers, one more device buffer (cl_profiles) for the resolved table, which is
+// uploaded whole
+int jg_claims_each(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                   const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
+                   const jg_select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out) {
+  if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out)) || (sel_out && (!select || !vals_out)) ||
+      (arena_len > 0 && !arena))
+    return -1;
+  if (njobs == 0) return 0;
+  if (ctx->poisoned.load()) {
+    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
+    return -2;
+  }
+  auto T = std::make_unique<jgclaims::Profiles>();
+  if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) {
+    ctx->set_err("jg_claims_each: no profile or more than 64, strings over 8192 bytes in all, or a profile with more "
+                 "than 16 audiences, expected strings over 4096 bytes or now_nsec >= 1e9");
+    return -1;
+  }
+  auto S = std::make_unique<jgclaims::Select>();
+  if (sel_out && !jgclaims::resolve_select(*select, S.get())) {
+    ctx->set_err("jg_claims_each: more than 8 names, a name that is empty, over 64 bytes or not printable ASCII "
+                 "without quote and backslash, or two equal names");
+    return -1;
+  }
+  for (size_t i = 0; i < njobs; ++i) {
+    const jg_cjob& J = jobs[i];
+    if (J.flags >= nexpect || J.off > arena_len || J.len > arena_len - J.off) {
+      ctx->set_err("jg_claims_each: job " + std::to_string(i) + " names no profile or has a span past the arena");
+      return -1;
+    }
+  }
+  try {
+    Device* d = ctx->devs[0].get();
+    std::lock_guard<std::mutex> g(d->cl_mu);
+    HIPCHK(hipSetDevice(d->id));
+    const hipStream_t s = d->clstream;
+    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
+    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
+    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
+    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
+    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
+    jgclaims::Profiles* t = (jgclaims::Profiles*)d->cl_profiles.get(sizeof(jgclaims::Profiles));
+    HIPCHK(hipMemcpyAsync(t, T.get(), sizeof(jgclaims::Profiles), hipMemcpyHostToDevice, s));
+    jgclaims::Select* sl = nullptr;
+    if (sel_out) {
+      sl = (jgclaims::Select*)d->cl_select.get(sizeof(jgclaims::Select));
+      HIPCHK(hipMemcpyAsync(sl, S.get(), sizeof(jgclaims::Select), hipMemcpyHostToDevice, s));
+    }
+    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
+    jg_claims* v = vals_out ? (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs) : nullptr;
+    jg_selected* q = sel_out ? (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs) : nullptr;
+    launch_claims_each(a, j, (int64_t)njobs, t, sl, o, v, q, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
+    if (v) HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
+    if (q) HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   } catch (const std::exception& e) {

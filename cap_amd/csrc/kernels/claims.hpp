@@ -30,6 +30,12 @@
 // Expect): a candidate mask over the names is armed when a depth-1 key opens,
 // narrowed per key byte and resolved at the closing quote; the value's first
 // byte latches the slot's offset and type, its end the length.
+//
+// The expected side is a template parameter of the scan (EX: slen / sbyte / auds
+// and the window's edges).  Expect is one; ProfileRef, one profile of a
+// Profiles table picked per token, is the other: claims_decide_each,
+// claims_extract_each and claims_select_each are the same three scans for a
+// batch whose tokens are held to different Expecteds.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -58,6 +64,15 @@ struct Expect {
   uint16_t len[kStrings];   // 0 issuer, 1 subject, 2 id, 3.. audiences
   uint16_t off[kStrings];
   uint8_t bytes[JG_EXPECT_MAX_BYTES];
+  // how the scan reads an expected side (Expect here, ProfileRef below)
+  JG_CL_HD uint32_t slen(uint32_t k) const { return len[k]; }
+  JG_CL_HD uint32_t sbyte(uint32_t k, uint32_t pos) const { return bytes[off[k] + pos]; }
+  JG_CL_HD uint32_t auds() const { return naud; }
+  JG_CL_HD int64_t hi() const { return hi_sec; }
+  JG_CL_HD int64_t lo() const { return lo_sec; }
+  JG_CL_HD int32_t lons() const { return lo_ns; }
+  JG_CL_HD int64_t exp_leeway() const { return exp_leeway_s; }
+  JG_CL_HD int64_t nbf_leeway() const { return nbf_leeway_s; }
 };
 
 // time.Time.Add of a duration to (sec, nsec): Go's truncating division
@@ -95,6 +110,87 @@ inline bool resolve(const jg_expect& x, Expect* E) {
   for (uint32_t b = o; b < JG_EXPECT_MAX_BYTES; ++b) E->bytes[b] = 0;
   return true;
 }
+
+// Up to JG_MAX_PROFILES resolved Expecteds for one call (jg_claims_each): the
+// per-token form of Expect.  A fixed-size header per profile and one pool of
+// JG_PROFILE_POOL_BYTES string bytes that the headers' offsets point into --
+// offsets, never pointers: the kernel holds the table in LDS and a pointer kept
+// there would be read back as a generic one.  64 x 120 B + 8 KiB is under 16 KiB
+// per block, where one Expect per profile would be 4216 B each.
+struct ProfileHeader {
+  int64_t hi_sec, lo_sec;
+  int64_t exp_leeway_s, nbf_leeway_s;
+  int32_t lo_ns;
+  uint32_t naud;
+  uint16_t len[kStrings];   // as Expect's
+  uint16_t off[kStrings];   // into Profiles::pool
+  uint32_t pad_;
+};
+struct Profiles {
+  uint32_t n;               // headers in use
+  uint32_t pool_used;       // pool bytes in use
+  ProfileHeader h[JG_MAX_PROFILES];
+  uint8_t pool[JG_PROFILE_POOL_BYTES];
+};
+static_assert(sizeof(ProfileHeader) == 120, "a profile header is 120 bytes");
+static_assert(sizeof(Profiles) == 8 + 120 * JG_MAX_PROFILES + JG_PROFILE_POOL_BYTES, "no padding in the table");
+static_assert(JG_PROFILE_POOL_BYTES <= 65536, "pool offsets are 16 bits");
+
+// Fills *T from n jg_expect.  False: n == 0 or over JG_MAX_PROFILES, a profile
+// resolve() refuses, strings over JG_PROFILE_POOL_BYTES in total.  Header p and
+// its pool bytes hold what resolve(x[p]) puts into an Expect; the unused
+// headers and the unused pool tail are zero.
+inline bool resolve_profiles(const jg_expect* x, uint32_t n, Profiles* T) {
+  if (!x || n == 0 || n > JG_MAX_PROFILES) return false;
+  uint32_t o = 0;
+  for (uint32_t p = 0; p < n; ++p) {
+    const jg_expect& X = x[p];
+    if (X.naud > JG_MAX_AUD || X.now_nsec >= (uint32_t)kNsPerSec) return false;
+    uint64_t total = (uint64_t)X.iss_len + X.sub_len + X.jti_len;
+    for (uint32_t k = 0; k < X.naud; ++k) total += X.aud_len[k];
+    if (total > JG_EXPECT_MAX_BYTES || (total && !X.strs)) return false;
+    if (o + total > JG_PROFILE_POOL_BYTES) return false;
+    ProfileHeader& H = T->h[p];
+    int32_t hi_ns;
+    time_add(X.now_sec + kUnixToInternal, X.now_nsec, X.skew_ns, &H.hi_sec, &hi_ns);
+    time_add(X.now_sec + kUnixToInternal, X.now_nsec, -X.skew_ns, &H.lo_sec, &H.lo_ns);
+    H.naud = X.naud;
+    H.exp_leeway_s = X.exp_leeway_s;
+    H.nbf_leeway_s = X.nbf_leeway_s;
+    H.pad_ = 0;
+    uint32_t so = 0;                                 // within this profile's strs
+    for (int k = 0; k < kStrings; ++k) {
+      const uint32_t l = k == 0 ? X.iss_len : k == 1 ? X.sub_len : k == 2 ? X.jti_len
+                         : (uint32_t)(k - 3) < X.naud ? X.aud_len[k - 3] : 0u;
+      H.len[k] = (uint16_t)l;
+      H.off[k] = (uint16_t)(l ? o : 0u);             // an empty string is never read: keep the offset in 16 bits
+      for (uint32_t b = 0; b < l; ++b) T->pool[o + b] = X.strs[so + b];
+      o += l;
+      so += l;
+    }
+  }
+  for (uint32_t p = n; p < JG_MAX_PROFILES; ++p) T->h[p] = ProfileHeader{};
+  for (uint32_t b = o; b < JG_PROFILE_POOL_BYTES; ++b) T->pool[b] = 0;
+  T->n = n;
+  T->pool_used = o;
+  return true;
+}
+
+// Profile p of a table as the scan reads an expected side: Expect's accessors
+// with a per-lane base.  The table is held by reference (in the kernel: the
+// block's LDS copy), so every read is an indexed read of that object.
+struct ProfileRef {
+  const Profiles& T;
+  uint32_t p;
+  JG_CL_HD uint32_t slen(uint32_t k) const { return T.h[p].len[k]; }
+  JG_CL_HD uint32_t sbyte(uint32_t k, uint32_t pos) const { return T.pool[T.h[p].off[k] + pos]; }
+  JG_CL_HD uint32_t auds() const { return T.h[p].naud; }
+  JG_CL_HD int64_t hi() const { return T.h[p].hi_sec; }
+  JG_CL_HD int64_t lo() const { return T.h[p].lo_sec; }
+  JG_CL_HD int32_t lons() const { return T.h[p].lo_ns; }
+  JG_CL_HD int64_t exp_leeway() const { return T.h[p].exp_leeway_s; }
+  JG_CL_HD int64_t nbf_leeway() const { return T.h[p].nbf_leeway_s; }
+};
 
 // The caller's claim names as the selecting scan reads them (a device buffer
 // copied to LDS beside Expect)
@@ -255,8 +351,8 @@ JG_CL_HD void pop(ScanT<M>& s, uint32_t is_obj) {
 }
 
 // the first byte of a value
-template <int M>
-JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const Expect& E) {
+template <int M, class EX>
+JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
   const uint32_t f = s.depth == 1u ? s.field : (uint32_t)F_NONE;
   const uint32_t elem = s.depth == 2u && s.aud_arr;        // an element of aud's array
   const uint32_t is_str3 = f - F_ISS < 3u, is_date = f - F_EXP < 3u;
@@ -267,8 +363,8 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const Expect& E) {
     s.ascii_only = f != F_NONE || elem;
     s.pos = 0;
     s.cmpf = elem ? (uint32_t)F_AUD : f;
-    s.cand = is_str3 ? (E.len[f - 1u] ? 1u << (f - 1u) : 0u)
-           : (f == F_AUD || elem) ? ((1u << E.naud) - 1u) << 3 : 0u;
+    s.cand = is_str3 ? (E.slen(f - 1u) ? 1u << (f - 1u) : 0u)
+           : (f == F_AUD || elem) ? ((1u << E.auds()) - 1u) << 3 : 0u;
     if constexpr (M >= kExtract) {
       const uint32_t in = s.dpos + 1u;                 // the first byte between the quotes
       s.iss_off = f == F_ISS ? in : s.iss_off;
@@ -333,8 +429,8 @@ JG_CL_HD void end_number(ScanT<M>& s) {
   s.st = ST_AFTER;
 }
 
-template <int M>
-JG_CL_HD void step(ScanT<M>& s, uint32_t c, const Expect& E, const Select* S) {
+template <int M, class EX>
+JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
   (void)S;
   if (s.st >= ST_NUM_MINUS && s.st <= ST_NUM_FRAC) {
     const uint32_t d = is_digit(c);
@@ -382,7 +478,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const Expect& E, const Select* S) {
           while (m) {
             const uint32_t k = (uint32_t)__builtin_ctz(m);
             m &= m - 1u;
-            hit |= E.len[k] == s.pos;
+            hit |= E.slen(k) == s.pos;
           }
           if (s.cmpf == F_AUD) s.aud_found |= hit;
           else if (s.cmpf != F_NONE) s.str_ok |= hit << s.cmpf;
@@ -415,7 +511,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const Expect& E, const Select* S) {
         while (m) {
           const uint32_t k = (uint32_t)__builtin_ctz(m);
           m &= m - 1u;
-          if (!(s.pos < E.len[k] && E.bytes[E.off[k] + s.pos] == c)) s.cand &= ~(1u << k);
+          if (!(s.pos < E.slen(k) && E.sbyte(k, s.pos) == c)) s.cand &= ~(1u << k);
         }
         ++s.pos;
       }
@@ -489,29 +585,29 @@ JG_CL_HD uint32_t sextet(uint32_t c) {
 }
 
 // jwt/jwt.go:117-199 on the scanned fields, in Validate's order
-template <int M>
-JG_CL_HD uint8_t verdict(const ScanT<M>& s, const Expect& E) {
+template <int M, class EX>
+JG_CL_HD uint8_t verdict(const ScanT<M>& s, const EX& E) {
   int64_t iat = s.iat, exp = s.exp, nbf = s.nbf;
   if (iat == 0 && exp == 0 && nbf == 0) return JG_CL_NO_TIME;
-  if (exp == 0) exp = (nbf > iat ? nbf : iat) + E.exp_leeway_s;
-  if (nbf == 0) nbf = iat != 0 ? iat : exp - E.nbf_leeway_s;
-  if (E.len[0] && !((s.str_ok >> F_ISS) & 1u)) return JG_CL_ISS;
-  if (E.len[1] && !((s.str_ok >> F_SUB) & 1u)) return JG_CL_SUB;
-  if (E.len[2] && !((s.str_ok >> F_JTI) & 1u)) return JG_CL_JTI;
-  if (E.naud && !s.aud_found) return JG_CL_AUD;
+  if (exp == 0) exp = (nbf > iat ? nbf : iat) + E.exp_leeway();
+  if (nbf == 0) nbf = iat != 0 ? iat : exp - E.nbf_leeway();
+  if (E.slen(0u) && !((s.str_ok >> F_ISS) & 1u)) return JG_CL_ISS;
+  if (E.slen(1u) && !((s.str_ok >> F_SUB) & 1u)) return JG_CL_SUB;
+  if (E.slen(2u) && !((s.str_ok >> F_JTI) & 1u)) return JG_CL_JTI;
+  if (E.auds() && !s.aud_found) return JG_CL_AUD;
   // time.Unix(x, 0) is (x + unixToInternal, 0): Before / After on (sec, nsec)
-  if (E.hi_sec < nbf + kUnixToInternal) return JG_CL_NBF;
+  if (E.hi() < nbf + kUnixToInternal) return JG_CL_NBF;
   const int64_t e = exp + kUnixToInternal;
-  if (E.lo_sec > e || (E.lo_sec == e && E.lo_ns > 0)) return JG_CL_EXP;
-  if (E.hi_sec < iat + kUnixToInternal) return JG_CL_IAT;
+  if (E.lo() > e || (E.lo() == e && E.lons() > 0)) return JG_CL_EXP;
+  if (E.hi() < iat + kUnixToInternal) return JG_CL_IAT;
   return JG_CL_OK;
 }
 
 // The scan of one segment: claims_decide's code and, with X, the record.  The
 // state is a local of this function (handing it in by reference costs the
 // verdict-only kernel a third of its registers again).
-template <int M, class Src>
-JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const Expect& E, jg_claims* out, const Select* S = nullptr,
+template <int M, class Src, class EX>
+JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* out, const Select* S = nullptr,
                               jg_selected* sel = nullptr) {
   if constexpr (M >= kExtract) *out = jg_claims{};                 // JG_CL_HOST: every byte zero
   if constexpr (M == kSelect) *sel = jg_selected{};
@@ -585,6 +681,27 @@ JG_CL_HD uint8_t claims_select(Src& src, uint32_t len, const Expect& E, const Se
   return scan_segment<kSelect>(src, len, E, out, &S, sel);
 }
 
+// The three functions above against profile p (< T.n) of a table: for every
+// segment the code and the records that the single-Expect function returns for
+// resolve(x[p]), byte for byte.  The same scan_segment, with the expected side
+// read through ProfileRef.
+template <class Src>
+JG_CL_HD uint8_t claims_decide_each(Src& src, uint32_t len, const Profiles& T, uint32_t p) {
+  const ProfileRef E{T, p};
+  return scan_segment<kVerdict>(src, len, E, nullptr);
+}
+template <class Src>
+JG_CL_HD uint8_t claims_extract_each(Src& src, uint32_t len, const Profiles& T, uint32_t p, jg_claims* out) {
+  const ProfileRef E{T, p};
+  return scan_segment<kExtract>(src, len, E, out);
+}
+template <class Src>
+JG_CL_HD uint8_t claims_select_each(Src& src, uint32_t len, const Profiles& T, uint32_t p, const Select& S,
+                                    jg_claims* out, jg_selected* sel) {
+  const ProfileRef E{T, p};
+  return scan_segment<kSelect>(src, len, E, out, &S, sel);
+}
+
 }  // namespace jgclaims
 
 #if defined(__HIPCC__)
@@ -599,4 +716,10 @@ void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n,
 void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
                           const jgclaims::Select* select, uint8_t* code_out, jg_claims* vals_out,
                           jg_selected* sel_out, hipStream_t s);
+// The three scans with a profile per job: `table` is a device jgclaims::Profiles
+// and jobs[i].flags (< table->n) names job i's profile.  sel_out: k_claims_select_each
+// (with `select` and vals_out); else vals_out: k_claims_extract_each; else k_claims_scan_each
+void launch_claims_each(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Profiles* table,
+                        const jgclaims::Select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
+                        hipStream_t s);
 #endif

@@ -249,6 +249,65 @@ class Validator:
             stats.update(scanned=scanned, host=host)
         return cols
 
+    # ---- the six entries above with an Expected per token: token i is held to
+    # expected[which[i]] (its issuer, audiences, subject, ID, SigningAlgorithms, Now
+    # and leeways), and its result is what the entry above returns for tokens[i]
+    # alone with that Expected.  One signature submission and one GPU scan for the
+    # batch, where a caller with several tenants had to make one call per tenant.
+    # ValueError: len(which) != the number of tokens, an index out of range, no
+    # Expected with tokens.
+    @staticmethod
+    def _natives(expected):
+        return [e._native() for e in expected]
+
+    def CheckBatchEach(self, tokens: Sequence, expected: Sequence[Expected], which: Sequence[int],
+                       stats: dict = None):
+        """CheckBatch with expected[which[i]] for tokens[i]."""
+        errs, scanned, host = self._impl.check_batch_each(list(tokens), self._natives(expected), list(which))
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return errs
+
+    def CheckBlobEach(self, blob: bytes, expected: Sequence[Expected], which, stats: dict = None) -> bytes:
+        """CheckBlob with expected[which[i]] for token i; `which` is a buffer of
+        uint32 (array("I"), a numpy uint32 array, ...), one per token."""
+        ok, scanned, host = self._impl.check_blob_each(blob, self._natives(expected), which)
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return ok
+
+    def RegisteredBatchEach(self, tokens: Sequence, expected: Sequence[Expected], which: Sequence[int],
+                            stats: dict = None):
+        """RegisteredBatch with expected[which[i]] for tokens[i]."""
+        rows, scanned, host = self._impl.registered_batch_each(list(tokens), self._natives(expected), list(which))
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return rows
+
+    def RegisteredBlobEach(self, blob: bytes, expected: Sequence[Expected], which, stats: dict = None) -> dict:
+        """RegisteredBlob with expected[which[i]] for token i; `which` as in CheckBlobEach."""
+        cols, scanned, host = self._impl.registered_blob_each(blob, self._natives(expected), which)
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
+    def SelectBatchEach(self, tokens: Sequence, names: Sequence[str], expected: Sequence[Expected],
+                        which: Sequence[int], stats: dict = None):
+        """SelectBatch with expected[which[i]] for tokens[i]; one name list for the batch."""
+        rows, scanned, host = self._impl.select_batch_each(list(tokens), list(names), self._natives(expected),
+                                                           list(which))
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return rows
+
+    def SelectBlobEach(self, blob: bytes, names: Sequence[str], expected: Sequence[Expected], which,
+                       stats: dict = None) -> dict:
+        """SelectBlob with expected[which[i]] for token i; `which` as in CheckBlobEach."""
+        cols, scanned, host = self._impl.select_blob_each(blob, list(names), self._natives(expected), which)
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
 
 def NewValidator(keyset: Optional[KeySet]):
     if keyset is None:

@@ -452,6 +452,42 @@ int jg_claims_select(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                      const jg_cjob* jobs, size_t njobs, const jg_expect* expect, const jg_select* select,
                      uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out);
 
+/* ---- the three scans with an Expected per token ----
+ * jg_claims_scan / jg_claims_extract / jg_claims_select for a batch whose tokens
+ * are held to different jwt.Expected (several tenants or OIDC clients behind one
+ * gateway): cap's Validate takes its Expected per call, and so does each job
+ * here.  `expects` holds nexpect profiles, each a jg_expect as above, and in
+ * this entry only jobs[i].flags is the index of job i's profile.  The mode
+ * follows the outputs:
+ *  - sel_out non-NULL: jg_claims_select (needs `select` and vals_out);
+ *  - else vals_out non-NULL: jg_claims_extract;
+ *  - else: jg_claims_scan.
+ * For every job, code_out[i], vals_out[i] and sel_out[i] are what that entry
+ * writes when it is called with expects[jobs[i].flags], byte for byte, always;
+ * with nexpect == 1 the call is the old entry.  Profiles only differ in what
+ * jg_expect holds: `select` is one name list for the call.
+ * The profiles travel as one table of at most JG_MAX_PROFILES headers and
+ * JG_PROFILE_POOL_BYTES string bytes in all (the kernel keeps it in 16 KiB of
+ * LDS), uploaded whole on every call into one more kept device buffer.
+ * Everything else is jg_claims_scan's: blocking, on the context's first device
+ * on the same stream of its own and under the same lock, device buffers kept
+ * between calls, njobs == 0 returns 0 without touching the buffers, -2 on an
+ * infrastructure error and in a context a device failure has made unusable.
+ * -1: nexpect 0 or over JG_MAX_PROFILES; a jobs[i].flags >= nexpect; a profile
+ * jg_claims_scan refuses (more than JG_MAX_AUD audiences, strings over
+ * JG_EXPECT_MAX_BYTES, now_nsec out of range); the profiles' strings over
+ * JG_PROFILE_POOL_BYTES in total; a `select` jg_claims_select refuses; sel_out
+ * without select or without vals_out; expects, jobs or code_out NULL with
+ * njobs > 0; a span past arena_len. */
+#define JG_MAX_PROFILES 64
+#define JG_PROFILE_POOL_BYTES 8192
+int jg_claims_each(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                   const jg_cjob* jobs, size_t njobs,
+                   const jg_expect* expects, uint32_t nexpect,
+                   const jg_select* select,      /* NULL unless sel_out */
+                   uint8_t* code_out, jg_claims* vals_out /* may be NULL */,
+                   jg_selected* sel_out /* may be NULL */);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 

@@ -113,6 +113,12 @@ static void* worker(void* arg) {
    * (e.g. "roles":["admin"],"scope":"read write", -- with the trailing comma) */
   const char* extra = getenv("TOKGEN_EXTRA");
   if (!extra) extra = "";
+  /* TOKGEN_TENANTS=P: token i belongs to tenant i % P, with an issuer and an
+   * audience of its own of the default ones' lengths ("https://t07.example/",
+   * "c07.example.com"); unset or 0: the default issuer and audience */
+  const char* te = getenv("TOKGEN_TENANTS");
+  const long tenants = te ? atol(te) : 0;
+  char iss[64] = "https://example.com/", aud[64] = "www.example.com";
   const size_t cap = 512 + padn + strlen(extra);
   char hdr[256], hb[512], sb[1500];
   char* pay = malloc(cap);
@@ -124,17 +130,21 @@ static void* worker(void* arg) {
   EC_KEY** ecs = calloc((size_t)j->nkeys, sizeof(EC_KEY*));     /* this thread's copies, made at first use */
   for (long i = j->lo; i < j->hi; ++i) {
     const int k = (int)(i % j->nkeys);
+    if (tenants > 0) {
+      snprintf(iss, sizeof iss, "https://t%02ld.example/", i % tenants);
+      snprintf(aud, sizeof aud, "c%02ld.example.com", i % tenants);
+    }
     snprintf(hdr, sizeof hdr, "{\"alg\":\"%s\",\"kid\":\"kid-%02d\",\"typ\":\"JWT\"}", j->alg, j->kid_base + k);
     if (padn)
       snprintf(pay, cap,
-               "{\"aud\":[\"www.example.com\"],\"exp\":1611699944,\"iat\":1611699344,"
-               "\"iss\":\"https://example.com/\",\"jti\":\"%ld\",\"nbf\":1611699344,\"pad\":\"%s\","
-               "%s\"sub\":\"alice@example.com\"}", i, padv, extra);
+               "{\"aud\":[\"%s\"],\"exp\":1611699944,\"iat\":1611699344,"
+               "\"iss\":\"%s\",\"jti\":\"%ld\",\"nbf\":1611699344,\"pad\":\"%s\","
+               "%s\"sub\":\"alice@example.com\"}", aud, iss, i, padv, extra);
     else
       snprintf(pay, cap,
-               "{\"aud\":[\"www.example.com\"],\"exp\":1611699944,\"iat\":1611699344,"
-               "\"iss\":\"https://example.com/\",\"jti\":\"%ld\",\"nbf\":1611699344,%s\"sub\":\"alice@example.com\"}",
-               i, extra);
+               "{\"aud\":[\"%s\"],\"exp\":1611699944,\"iat\":1611699344,"
+               "\"iss\":\"%s\",\"jti\":\"%ld\",\"nbf\":1611699344,%s\"sub\":\"alice@example.com\"}",
+               aud, iss, i, extra);
     size_t hl = b64url((const unsigned char*)hdr, strlen(hdr), hb);
     size_t pl = b64url((const unsigned char*)pay, strlen(pay), pb);
     char* si = malloc(hl + pl + 2);
