@@ -24,7 +24,8 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_submit", "jg_wait", "jg_set_chunk", "jg_set_zero_copy", "jg_set_table_budget", "jg_keys_wait_tables",
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
-           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each"]
+           "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
+           "jg_claims_paths"]
 
 
 class JgKey(ctypes.Structure):
@@ -106,6 +107,14 @@ class JgSelected(ctypes.Structure):
 
 assert ctypes.sizeof(JgSelected) == 80
 
+MAX_PATHS, PATH_MAX_COMP = 8, 4              # JG_MAX_PATHS, JG_PATH_MAX_COMP
+
+
+class JgPaths(ctypes.Structure):
+    """jg_paths: the caller's claim paths, their components back to back in `names`"""
+    _fields_ = [("names", ctypes.c_void_p), ("n", ctypes.c_uint32), ("ncomp", ctypes.c_uint32 * MAX_PATHS),
+                ("comp_len", (ctypes.c_uint32 * PATH_MAX_COMP) * MAX_PATHS)]
+
 _lib = None
 
 
@@ -151,6 +160,8 @@ def lib():
                                        ctypes.POINTER(JgSelect), vp, vp, vp]
         L.jg_claims_each.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
                                      ctypes.c_uint32, ctypes.POINTER(JgSelect), vp, vp, vp]
+        L.jg_claims_paths.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                      ctypes.c_uint32, ctypes.POINTER(JgPaths), vp, vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -493,6 +504,60 @@ class Context:
         if mode == "extract":
             return out.raw[:n], v
         return out.raw[:n], v, (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n])
+
+    def claims_paths(self, arena_bytes, jobs, expects, paths, nexpect=None, null=()):
+        """jg_claims_paths: claims_each's selecting form for members named by path.
+        `jobs`: (off, len, profile) triples; `expects`: a list of dicts as
+        claims_scan takes one; `paths`: a list of paths, each a sequence of
+        components (bytes) -> (codes, vals, sels) as claims_select returns them.
+        The outputs are poisoned with 0xee before the call.  `nexpect` overrides
+        the count passed to the ABI and `null` names arguments ("paths", "vals",
+        "sels") to pass as NULL (both for its argument checks)."""
+        n = len(jobs)
+        cj = (JgCJob * max(1, n))()
+        for i, (off, ln, prof) in enumerate(jobs):
+            cj[i].off, cj[i].len, cj[i].flags = off, ln, prof
+        es = (JgExpect * max(1, len(expects)))()
+        keep = []
+        for e, expect in zip(es, expects):
+            auds = [bytes(a) for a in expect.get("audiences", [])]
+            strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
+            blob = b"".join(strs + auds)
+            keep.append(ctypes.create_string_buffer(blob, max(1, len(blob))))
+            e.strs = ctypes.cast(keep[-1], ctypes.c_void_p)
+            e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
+            e.naud = len(auds)
+            for k, a in enumerate(auds[:MAX_AUD]):
+                e.aud_len[k] = len(a)
+            e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
+            e.skew_ns = int(expect["skew_ns"])
+            e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
+        paths = [[bytes(c) for c in path] for path in paths]
+        ps = JgPaths()
+        ps.n = len(paths)
+        nblob = b""
+        for k, path in enumerate(paths[:MAX_PATHS]):
+            ps.ncomp[k] = len(path)
+            for d, c in enumerate(path[:PATH_MAX_COMP]):        # past what the struct holds the path is refused on its count
+                ps.comp_len[k][d] = len(c)
+                nblob += c
+        nkeep = ctypes.create_string_buffer(nblob, max(1, len(nblob)))
+        ps.names = ctypes.cast(nkeep, ctypes.c_void_p)
+        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
+        vals = (JgClaims * max(1, n))()
+        ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
+        sels = (JgSelected * max(1, n))()
+        ctypes.memset(sels, 0xee, ctypes.sizeof(sels))
+        buf = bytes(arena_bytes) or b"\0"
+        rc = lib().jg_claims_paths(self.h, buf, len(arena_bytes), cj, n, es,
+                                   len(expects) if nexpect is None else nexpect,
+                                   None if "paths" in null else ctypes.byref(ps), out,
+                                   None if "vals" in null else ctypes.cast(vals, ctypes.c_void_p),
+                                   None if "sels" in null else ctypes.cast(sels, ctypes.c_void_p))
+        if rc != 0:
+            raise JgError(f"jg_claims_paths rc={rc}: {self.error()}")
+        return (out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n]),
+                (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n]))
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

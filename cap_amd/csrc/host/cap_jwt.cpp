@@ -1981,8 +1981,10 @@ RegisteredClaims claims_of_record(std::string_view seg, const jg_claims& v) {
 // the caller's names (`select`; nullptr: a name list the ABI does not take, every
 // token takes the host path), the jg_selected records lie behind the jg_claims
 // records, record(...) also receives token i's jg_selected and claims(...) the
-// verified claims map of the host-path token.
-constexpr int kCheckMode = 0, kRegisteredMode = 1, kSelectMode = 2;
+// verified claims map of the host-path token.  M = kPathMode: kSelectMode with
+// the caller's paths (`paths`, nullptr as for `select`) and jg_claims_paths as
+// the scan, with one Expected too (a table of one profile).
+constexpr int kCheckMode = 0, kRegisteredMode = 1, kSelectMode = 2, kPathMode = 3;
 
 // One Expected as the scan takes it (include/jg.h jg_expect) and the clock its
 // tokens are held to.  scannable == false: one the ABI does not take (more than
@@ -2031,7 +2033,8 @@ void resolve_scan_profile(const Expected& expected, int64_t now, ScanProfile* P)
 // as every token of an unscannable Expected does, so no result depends on the caps.
 template <int M, bool Each, class Put>
 void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected* exps, size_t nexp,
-                const uint32_t* which, CheckStats* stats, Put&& put, const jg_select* select = nullptr) {
+                const uint32_t* which, CheckStats* stats, Put&& put, const jg_select* select = nullptr,
+                const jg_paths* paths = nullptr) {
   constexpr bool X = M >= kRegisteredMode;
   // a token that is not accepted carries no claims
   auto reject = [&](size_t c, size_t i, std::string&& err) {
@@ -2057,6 +2060,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
       resolve_scan_profile(exps[p], exps[p].has_now ? exps[p].now_unix_ns : wall, &prof[p]);
       bool fits = prof[p].scannable;
       if constexpr (M == kSelectMode) fits = fits && select != nullptr;
+      if constexpr (M == kPathMode) fits = fits && paths != nullptr;
       if constexpr (Each)
         fits = fits && exs.size() < JG_MAX_PROFILES && pool + prof[p].strs.size() <= JG_PROFILE_POOL_BYTES;
       if (!fits) continue;
@@ -2074,7 +2078,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   // speed, no page faults in steady state).
   Engine& eng = ks_->engine();
   const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | selected | codes
-  const size_t sel_bytes = M == kSelectMode ? n * sizeof(jg_selected) : 0;
+  const size_t sel_bytes = M >= kSelectMode ? n * sizeof(jg_selected) : 0;
   Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + rec_bytes + sel_bytes + 16);
   jg_cjob* const jobs = (jg_cjob*)scanbuf.get();
   jg_claims* const recs = (jg_claims*)(scanbuf.get() + n * sizeof(jg_cjob));
@@ -2112,7 +2116,9 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     pt.lap("scan-jobs");
     try {
       const jg_expect& ex = exs[0];
-      if constexpr (Each)
+      if constexpr (M == kPathMode)
+        eng.claims_paths(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), paths, code, recs, sels, true);
+      else if constexpr (Each)
         eng.claims_each(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(),
                         M == kSelectMode ? select : nullptr, code, X ? recs : nullptr,
                         M == kSelectMode ? sels : nullptr, true);
@@ -2163,7 +2169,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
           RegisteredClaims rc;
           Result v = validate_claims(r.claims, t.view(), expected, now, &rc);
           if (!v.ok) reject(c, i, std::move(v.err));
-          else if constexpr (M == kSelectMode) put.claims(c, i, std::move(rc), r.claims);
+          else if constexpr (M >= kSelectMode) put.claims(c, i, std::move(rc), r.claims);
           else put.claims(c, i, std::move(rc));
         } else {
           Result v = validate_claims(r.claims, t.view(), expected, now);
@@ -2180,7 +2186,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
       if constexpr (X) {
         // the payload segment ends the signing input; its length is the job's
         if (code[i] != JG_CL_OK) reject(c, i, std::string(claim_code_error(code[i])));
-        else if constexpr (M == kSelectMode)
+        else if constexpr (M >= kSelectMode)
           put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i], sels[i]);
         else
           put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i]);
@@ -2354,7 +2360,11 @@ struct SelectNames {
   jg_select abi{};
   std::vector<int> slot;                           // names[k] is slot[k] of a jg_selected
   bool usable = true;
-  explicit SelectNames(const std::vector<std::string>& names) : slot(names.size(), -1) {
+  const std::vector<std::string>& names;
+  size_t size() const { return names.size(); }
+  // the entry of a host-path token's verified claims map
+  const json::Value* find(const json::Value& all, size_t k) const { return all.get(names[k]); }
+  explicit SelectNames(const std::vector<std::string>& names) : slot(names.size(), -1), names(names) {
     std::vector<std::string_view> uniq;
     for (size_t k = 0; k < names.size(); ++k) {
       const std::string& nm = names[k];
@@ -2377,6 +2387,57 @@ struct SelectNames {
     abi.names = (const uint8_t*)bytes.data();
   }
   const jg_select* select() const { return usable ? &abi : nullptr; }
+};
+
+// The caller's paths as the scan takes them (jg_paths), as SelectNames holds
+// names: equal paths share a slot; usable == false: every token goes the host path.
+struct SelectPaths {
+  std::string bytes;
+  jg_paths abi{};
+  std::vector<int> slot;                           // paths[k] is slot[k] of a jg_selected
+  bool usable = true;
+  const std::vector<ClaimPath>& paths;
+  size_t size() const { return paths.size(); }
+  // the claims map walked along path k: every value on the way an object that holds the key
+  const json::Value* find(const json::Value& all, size_t k) const {
+    const json::Value* cur = &all;
+    for (const std::string& comp : paths[k]) {
+      if (cur->kind != json::Value::Object) return nullptr;
+      cur = cur->get(comp);
+      if (!cur) return nullptr;
+    }
+    return cur;
+  }
+  explicit SelectPaths(const std::vector<ClaimPath>& paths) : slot(paths.size(), -1), paths(paths) {
+    std::vector<const ClaimPath*> uniq;
+    for (size_t k = 0; k < paths.size(); ++k) {
+      const ClaimPath& path = paths[k];
+      if (path.empty()) throw std::invalid_argument("capjwt: a claim path has no component");
+      if (path.size() > JG_PATH_MAX_COMP) usable = false;
+      for (const std::string& comp : path) {
+        if (comp.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim path holds a NUL byte");
+        if (comp.empty() || comp.size() > JG_SELECT_NAME_MAX) usable = false;
+        for (unsigned char c : comp)
+          if (c < 0x20 || c > 0x7e || c == '"' || c == '\\') usable = false;
+      }
+      size_t u = 0;
+      while (u < uniq.size() && *uniq[u] != path) ++u;
+      if (u == uniq.size()) uniq.push_back(&path);
+      slot[k] = (int)u;
+    }
+    if (uniq.size() > JG_MAX_PATHS) usable = false;
+    if (!usable) return;
+    for (size_t u = 0; u < uniq.size(); ++u) {
+      abi.ncomp[u] = (uint32_t)uniq[u]->size();
+      for (size_t d = 0; d < uniq[u]->size(); ++d) {
+        abi.comp_len[u][d] = (uint32_t)(*uniq[u])[d].size();
+        bytes += (*uniq[u])[d];
+      }
+    }
+    abi.n = (uint32_t)uniq.size();
+    abi.names = (const uint8_t*)bytes.data();
+  }
+  const jg_paths* select() const { return usable ? &abi : nullptr; }
 };
 
 // The claims-map entry a slot of the scan's record stands for.  A string whose
@@ -2421,38 +2482,37 @@ uint8_t sel_type_of(const json::Value& v) {
   }
 }
 
+template <class Keys>                              // SelectNames or SelectPaths
 struct SelectRowSink {                             // SelectBatch: one SelectResult per token
   std::vector<SelectResult>& out;
-  const std::vector<std::string>& names;
-  const SelectNames& N;
+  const Keys& N;
   void reject(size_t, size_t i, std::string&& err) { out[i].err = std::move(err); }
   void record(size_t, size_t i, std::string_view seg, const jg_claims& v, const jg_selected& q) {
     out[i].ok = true;
     out[i].claims = claims_of_record(seg, v);
-    out[i].values.resize(names.size());
-    for (size_t k = 0; k < names.size(); ++k) out[i].values[k] = value_of_slot(seg, q, N.slot[k]);
+    out[i].values.resize(N.size());
+    for (size_t k = 0; k < N.size(); ++k) out[i].values[k] = value_of_slot(seg, q, N.slot[k]);
   }
   void claims(size_t, size_t i, RegisteredClaims&& c, const json::Value& all) {
     out[i].ok = true;
     out[i].claims = std::move(c);
-    out[i].values.resize(names.size());
-    for (size_t k = 0; k < names.size(); ++k)
-      if (const json::Value* m = all.get(names[k])) out[i].values[k] = *m;
+    out[i].values.resize(N.size());
+    for (size_t k = 0; k < N.size(); ++k)
+      if (const json::Value* m = N.find(all, k)) out[i].values[k] = *m;
   }
 };
 
 // SelectCols: ColumnSink for the registered columns; per name the type and the
 // number are written in place and the text goes to the merge thread's part
+template <class Keys>
 struct SelectColumnSink {
   ColumnSink reg;
   const SelectColumns& S;
-  const std::vector<std::string>& names;
-  const SelectNames& N;
+  const Keys& N;
   const Chunks& ch;
   std::vector<std::vector<std::string>> text;      // [chunk][name]
-  SelectColumnSink(const SelectColumns& s, const std::vector<std::string>& nm, const SelectNames& sn, const Chunks& chunks)
-      : reg(s.reg, chunks), S(s), names(nm), N(sn), ch(chunks),
-        text(chunks.count(), std::vector<std::string>(nm.size())) {}
+  SelectColumnSink(const SelectColumns& s, const Keys& sn, const Chunks& chunks)
+      : reg(s.reg, chunks), S(s), N(sn), ch(chunks), text(chunks.count(), std::vector<std::string>(sn.size())) {}
   void cell(size_t c, size_t i, size_t k, const json::Value* v, uint8_t type) {
     std::string& T = text[c][k];
     if (v) {
@@ -2465,11 +2525,11 @@ struct SelectColumnSink {
   }
   void reject(size_t c, size_t i, std::string&& err) {
     reg.reject(c, i, std::move(err));
-    for (size_t k = 0; k < names.size(); ++k) cell(c, i, k, nullptr, JG_SEL_ABSENT);
+    for (size_t k = 0; k < N.size(); ++k) cell(c, i, k, nullptr, JG_SEL_ABSENT);
   }
   void record(size_t c, size_t i, std::string_view seg, const jg_claims& v, const jg_selected& q) {
     reg.record(c, i, seg, v);
-    for (size_t k = 0; k < names.size(); ++k) {
+    for (size_t k = 0; k < N.size(); ++k) {
       const int slot = N.slot[k];
       if (q.type[slot] == JG_SEL_STRING) {         // the common case: straight from the payload into the part
         append_span(text[c][k], seg, q.off[slot], q.len[slot]);
@@ -2482,15 +2542,15 @@ struct SelectColumnSink {
   }
   void claims(size_t c, size_t i, RegisteredClaims&& cl, const json::Value& all) {
     reg.claims(c, i, std::move(cl));
-    for (size_t k = 0; k < names.size(); ++k) {
-      const json::Value* m = all.get(names[k]);
+    for (size_t k = 0; k < N.size(); ++k) {
+      const json::Value* m = N.find(all, k);
       cell(c, i, k, m, m ? sel_type_of(*m) : (uint8_t)JG_SEL_ABSENT);
     }
   }
   void finish() {
     reg.finish();
     const size_t nc = text.size();
-    for (size_t k = 0; k < names.size(); ++k) {
+    for (size_t k = 0; k < N.size(); ++k) {
       std::vector<size_t> base(nc + 1, 0);
       for (size_t c = 0; c < nc; ++c) base[c + 1] = base[c] + text[c][k].size();
       char* const data = (char*)S.alloc_text(k, base[nc]);
@@ -2510,7 +2570,7 @@ std::vector<SelectResult> Validator::SelectBatch(const std::vector<std::string_v
                                                  const std::vector<std::string>& names, CheckStats* stats) {
   const SelectNames N(names);
   std::vector<SelectResult> out(tokens.size());
-  check_core<kSelectMode, false>(ks_, tokens, &expected, 1, nullptr, stats, SelectRowSink{out, names, N}, N.select());
+  check_core<kSelectMode, false>(ks_, tokens, &expected, 1, nullptr, stats, SelectRowSink<SelectNames>{out, N}, N.select());
   return out;
 }
 
@@ -2519,7 +2579,7 @@ void Validator::SelectCols(const std::vector<std::string_view>& tokens, const Ex
   if (out.names.size() != names.size()) throw std::invalid_argument("capjwt: SelectCols: one column set per name");
   const SelectNames N(names);
   const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
-  SelectColumnSink sink(out, names, N, ch);
+  SelectColumnSink<SelectNames> sink(out, N, ch);
   check_core<kSelectMode, false>(ks_, tokens, &expected, 1, nullptr, stats, sink, N.select());
   PhaseTimer pt("check");
   sink.finish();
@@ -2602,7 +2662,7 @@ std::vector<SelectResult> Validator::SelectBatchEach(const std::vector<std::stri
   const SelectNames N(names);
   std::vector<SelectResult> out(tokens.size());
   check_core<kSelectMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
-                                SelectRowSink{out, names, N}, N.select());
+                                SelectRowSink<SelectNames>{out, N}, N.select());
   return out;
 }
 
@@ -2613,8 +2673,57 @@ void Validator::SelectColsEach(const std::vector<std::string_view>& tokens, cons
   each_args("SelectColsEach", tokens, expected, which);
   const SelectNames N(names);
   const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
-  SelectColumnSink sink(out, names, N, ch);
+  SelectColumnSink<SelectNames> sink(out, N, ch);
   check_core<kSelectMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats, sink, N.select());
+  PhaseTimer pt("check");
+  sink.finish();
+  pt.lap("columns");
+}
+
+// ---- the four Select entries by path
+std::vector<SelectResult> Validator::SelectBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                                 const ClaimPaths& paths, CheckStats* stats) {
+  const SelectPaths N(paths.paths);
+  std::vector<SelectResult> out(tokens.size());
+  check_core<kPathMode, false>(ks_, tokens, &expected, 1, nullptr, stats, SelectRowSink<SelectPaths>{out, N}, nullptr,
+                               N.select());
+  return out;
+}
+
+void Validator::SelectCols(const std::vector<std::string_view>& tokens, const Expected& expected,
+                           const ClaimPaths& paths, const SelectColumns& out, CheckStats* stats) {
+  if (out.names.size() != paths.paths.size()) throw std::invalid_argument("capjwt: SelectCols: one column set per path");
+  const SelectPaths N(paths.paths);
+  const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
+  SelectColumnSink<SelectPaths> sink(out, N, ch);
+  check_core<kPathMode, false>(ks_, tokens, &expected, 1, nullptr, stats, sink, nullptr, N.select());
+  PhaseTimer pt("check");
+  sink.finish();
+  pt.lap("columns");
+}
+
+std::vector<SelectResult> Validator::SelectBatchEach(const std::vector<std::string_view>& tokens,
+                                                     const std::vector<Expected>& expected,
+                                                     const std::vector<uint32_t>& which,
+                                                     const ClaimPaths& paths, CheckStats* stats) {
+  each_args("SelectBatchEach", tokens, expected, which);
+  const SelectPaths N(paths.paths);
+  std::vector<SelectResult> out(tokens.size());
+  check_core<kPathMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                              SelectRowSink<SelectPaths>{out, N}, nullptr, N.select());
+  return out;
+}
+
+void Validator::SelectColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                               const std::vector<uint32_t>& which, const ClaimPaths& paths,
+                               const SelectColumns& out, CheckStats* stats) {
+  if (out.names.size() != paths.paths.size()) throw std::invalid_argument("capjwt: SelectColsEach: one column set per path");
+  each_args("SelectColsEach", tokens, expected, which);
+  const SelectPaths N(paths.paths);
+  const Chunks ch = make_chunks(tokens.size(), host_threads());      // check_core's own chunks
+  SelectColumnSink<SelectPaths> sink(out, N, ch);
+  check_core<kPathMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats, sink, nullptr,
+                              N.select());
   PhaseTimer pt("check");
   sink.finish();
   pt.lap("columns");
@@ -2700,6 +2809,25 @@ void Engine::claims_each(const uint8_t* arena, size_t arena_len, const void* job
   if (rc == -1)
     throw std::logic_error(std::string("capjwt: jg_claims_each rejected the host's jobs: ") + jg_last_error(ctx_));
   if (rc != 0) fail_device(std::string("capjwt: jg_claims_each: ") + jg_last_error(ctx_));
+}
+
+// ... and jg_claims_paths (the Select entries by path)
+extern "C" __attribute__((weak)) int jg_claims_paths(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
+                                                     const jg_expect*, uint32_t, const jg_paths*, uint8_t*, jg_claims*,
+                                                     jg_selected*);
+
+void Engine::claims_paths(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                          uint32_t nexpect, const void* paths, uint8_t* codes, void* vals, void* sels,
+                          bool inside_verify) {
+  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
+  if (!inside_verify) life.lock();
+  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
+  if (!jg_claims_paths) fail_device("capjwt: jg_claims_paths: not provided by the loaded verifier library");
+  const int rc = jg_claims_paths(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects,
+                                 nexpect, (const jg_paths*)paths, codes, (jg_claims*)vals, (jg_selected*)sels);
+  if (rc == -1)
+    throw std::logic_error(std::string("capjwt: jg_claims_paths rejected the host's jobs: ") + jg_last_error(ctx_));
+  if (rc != 0) fail_device(std::string("capjwt: jg_claims_paths: ") + jg_last_error(ctx_));
 }
 
 namespace {

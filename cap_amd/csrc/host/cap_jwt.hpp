@@ -209,6 +209,11 @@ class Engine {
   void claims_each(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                    uint32_t nexpect, const void* select, uint8_t* codes, void* vals, void* sels,
                    bool inside_verify = false);
+  // jg_claims_each's selecting form for members named by path (jg_claims_paths):
+  // `paths` is a jg_paths
+  void claims_paths(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                    uint32_t nexpect, const void* paths, uint8_t* codes, void* vals, void* sels,
+                    bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -479,6 +484,15 @@ struct SelectResult {
   RegisteredClaims claims;
   std::vector<std::optional<json::Value>> values;     // one per name
 };
+// A claim inside objects, by the keys that lead to it: {"realm_access", "roles"}
+// is claims["realm_access"]["roles"].  Components are literal keys; nothing in
+// them is parsed as a separator.
+using ClaimPath = std::vector<std::string>;
+// The paths of one Select call.  A type of its own, so that a braced list of
+// names ({"scope", "roles"}) still names the overload that takes names alone.
+struct ClaimPaths {
+  std::vector<ClaimPath> paths;
+};
 // SelectBatch as columns (SelectBlob): RegisteredColumns plus, per name, the
 // value's type, its number and its text.  Rows of a rejected token are empty.
 struct SelectColumns {
@@ -575,6 +589,28 @@ class Validator {
                                             const std::vector<std::string>& names, CheckStats* stats = nullptr);
   void SelectColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
                       const std::vector<uint32_t>& which, const std::vector<std::string>& names,
+                      const SelectColumns& out, CheckStats* stats = nullptr);
+  // The four Select entries for claims inside objects: values[k] (column set
+  // k) is what walking ValidateBatch's claims map along paths[k] reaches -- at
+  // each component the current value must be an object and hold the key, else
+  // the claim is absent; arrays are never descended.  A one-component path is
+  // the name.  The scan matches component j against the keys at depth j of the
+  // object that components 1..j-1 opened (jg_claims_paths) and latches the value
+  // as for a name; a token the scan leaves to the host walks its verified claims
+  // map.  A path list the scan does not take (more than JG_MAX_PATHS distinct
+  // paths, a path of more than JG_PATH_MAX_COMP components, a component a name
+  // list would not be taken for) sends every token to the host path; equal paths
+  // share a slot.  Throws std::invalid_argument for a path without components
+  // and for a component with a NUL byte.
+  std::vector<SelectResult> SelectBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                        const ClaimPaths& paths, CheckStats* stats = nullptr);
+  void SelectCols(const std::vector<std::string_view>& tokens, const Expected& expected,
+                  const ClaimPaths& paths, const SelectColumns& out, CheckStats* stats = nullptr);
+  std::vector<SelectResult> SelectBatchEach(const std::vector<std::string_view>& tokens,
+                                            const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
+                                            const ClaimPaths& paths, CheckStats* stats = nullptr);
+  void SelectColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                      const std::vector<uint32_t>& which, const ClaimPaths& paths,
                       const SelectColumns& out, CheckStats* stats = nullptr);
  private:
   KeySet* ks_;

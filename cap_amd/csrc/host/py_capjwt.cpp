@@ -557,16 +557,23 @@ PYBIND11_MODULE(_capjwt_host, m) {
     lap("registered");
     return py::make_tuple(C.dict(), st.scanned, st.host);
   };
-  auto py_select_batch = [](PyValidator& s, py::sequence toks, std::vector<std::string> names, const Who& who) {
+  using PathList = std::vector<ClaimPath>;
+  // a name list as it is, a path list as the ClaimPaths the path overloads take
+  struct AsKeys {
+    const std::vector<std::string>& operator()(const std::vector<std::string>& names) const { return names; }
+    ClaimPaths operator()(const PathList& paths) const { return ClaimPaths{paths}; }
+  };
+  auto py_select_batch = [](PyValidator& s, py::sequence toks, const auto& names, const Who& who) {
     // registered_batch with the claims `names` name:
-    // ([(claims dict or None, {name: value} or None, error or None)], scanned, host)
+    // ([(claims dict or None, {name: value} or None, error or None)], scanned, host);
+    // for a list of paths the values are keyed by the path's index in it
     auto v = as_strings(toks);
     std::vector<SelectResult> rs;
     CheckStats st;
     {
       py::gil_scoped_release rel;
-      rs = who.es ? s.v->SelectBatchEach(views(v), *who.es, *who.w, names, &st)
-                  : s.v->SelectBatch(views(v), *who.e, names, &st);
+      rs = who.es ? s.v->SelectBatchEach(views(v), *who.es, *who.w, AsKeys{}(names), &st)
+                  : s.v->SelectBatch(views(v), *who.e, AsKeys{}(names), &st);
     }
     py::list out(rs.size());
     for (size_t i = 0; i < rs.size(); ++i) {
@@ -576,12 +583,15 @@ PYBIND11_MODULE(_capjwt_host, m) {
       }
       py::dict vals;
       for (size_t k = 0; k < names.size(); ++k)
-        if (rs[i].values[k]) vals[py::str(names[k])] = to_py(*rs[i].values[k]);
+        if (rs[i].values[k]) {
+          if constexpr (std::is_same_v<std::decay_t<decltype(names)>, PathList>) vals[py::int_(k)] = to_py(*rs[i].values[k]);
+          else vals[py::str(names[k])] = to_py(*rs[i].values[k]);
+        }
       out[i] = py::make_tuple(claims_py(rs[i].claims), vals, py::none());
     }
     return py::make_tuple(out, st.scanned, st.host);
   };
-  auto py_select_blob = [](PyValidator& s, py::bytes blob, std::vector<std::string> names, const Who& who) {
+  auto py_select_blob = [](PyValidator& s, py::bytes blob, const auto& names, const Who& who) {
     // registered_blob with, per name, the value's type / number / text columns
     char* bp = nullptr;
     Py_ssize_t bn = 0;
@@ -619,8 +629,8 @@ PYBIND11_MODULE(_capjwt_host, m) {
     CheckStats st;
     {
       py::gil_scoped_release rel;
-      if (who.es) s.v->SelectColsEach(toks, *who.es, *who.w, names, S, &st);
-      else s.v->SelectCols(toks, *who.e, names, S, &st);
+      if (who.es) s.v->SelectColsEach(toks, *who.es, *who.w, AsKeys{}(names), S, &st);
+      else s.v->SelectCols(toks, *who.e, AsKeys{}(names), S, &st);
     }
     lap("select");
     py::dict d = C.dict();
@@ -737,6 +747,21 @@ PYBIND11_MODULE(_capjwt_host, m) {
                                  const std::vector<Expected>& es, py::buffer which) {
         const std::vector<uint32_t> w = which_of(which);
         return py_select_blob(s, blob, names, Who{nullptr, &es, &w});
+      })
+      .def("select_paths_batch", [=](PyValidator& s, py::sequence toks, PathList paths, const Expected& e) {
+        return py_select_batch(s, toks, paths, Who{&e, nullptr, nullptr});
+      })
+      .def("select_paths_batch_each", [=](PyValidator& s, py::sequence toks, PathList paths,
+                                        const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
+        return py_select_batch(s, toks, paths, Who{nullptr, &es, &which});
+      })
+      .def("select_paths_blob", [=](PyValidator& s, py::bytes blob, PathList paths, const Expected& e) {
+        return py_select_blob(s, blob, paths, Who{&e, nullptr, nullptr});
+      })
+      .def("select_paths_blob_each", [=](PyValidator& s, py::bytes blob, PathList paths,
+                                       const std::vector<Expected>& es, py::buffer which) {
+        const std::vector<uint32_t> w = which_of(which);
+        return py_select_blob(s, blob, paths, Who{nullptr, &es, &w});
       })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {

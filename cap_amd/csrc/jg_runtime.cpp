@@ -718,6 +718,7 @@ struct Device {
   Grow cl_vals;                     // jg_claims_extract's records
   Grow cl_select, cl_sel;           // jg_claims_select's resolved names and its records
   Grow cl_profiles;                 // jg_claims_each's resolved table
+  Grow cl_paths;                    // jg_claims_paths' resolved paths
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -3613,6 +3614,69 @@ int jg_claims_each(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
     if (v) HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
     if (q) HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(e.what());
+    return -2;
+  }
+}
+
+// jg_claims_each's selecting form with paths in the place of names: the same
+// checks, stream, lock and kept buffers, one more device buffer (cl_paths) for
+// the resolved paths, which is uploaded whole
+int jg_claims_paths(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                    const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
+                    const jg_paths* paths, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out) {
+  if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out || !paths || !vals_out || !sel_out)) ||
+      (arena_len > 0 && !arena))
+    return -1;
+  if (njobs == 0) return 0;
+  if (ctx->poisoned.load()) {
+    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
+    return -2;
+  }
+  auto T = std::make_unique<jgclaims::Profiles>();
+  if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) {
+    ctx->set_err("jg_claims_paths: no profile or more than 64, strings over 8192 bytes in all, or a profile with more "
+                 "than 16 audiences, expected strings over 4096 bytes or now_nsec >= 1e9");
+    return -1;
+  }
+  auto P = std::make_unique<jgclaims::Paths>();
+  if (!jgclaims::resolve_paths(*paths, P.get())) {
+    ctx->set_err("jg_claims_paths: more than 8 paths, a path of no or more than 4 components, a component that is "
+                 "empty, over 64 bytes or not printable ASCII without quote and backslash, or two equal paths");
+    return -1;
+  }
+  for (size_t i = 0; i < njobs; ++i) {
+    const jg_cjob& J = jobs[i];
+    if (J.flags >= nexpect || J.off > arena_len || J.len > arena_len - J.off) {
+      ctx->set_err("jg_claims_paths: job " + std::to_string(i) + " names no profile or has a span past the arena");
+      return -1;
+    }
+  }
+  try {
+    Device* d = ctx->devs[0].get();
+    std::lock_guard<std::mutex> g(d->cl_mu);
+    HIPCHK(hipSetDevice(d->id));
+    const hipStream_t s = d->clstream;
+    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
+    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
+    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
+    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
+    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
+    jgclaims::Profiles* t = (jgclaims::Profiles*)d->cl_profiles.get(sizeof(jgclaims::Profiles));
+    HIPCHK(hipMemcpyAsync(t, T.get(), sizeof(jgclaims::Profiles), hipMemcpyHostToDevice, s));
+    jgclaims::Paths* pp = (jgclaims::Paths*)d->cl_paths.get(sizeof(jgclaims::Paths));
+    HIPCHK(hipMemcpyAsync(pp, P.get(), sizeof(jgclaims::Paths), hipMemcpyHostToDevice, s));
+    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
+    jg_claims* v = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
+    jg_selected* q = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
+    launch_claims_paths(a, j, (int64_t)njobs, t, pp, o, v, q, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   } catch (const std::exception& e) {

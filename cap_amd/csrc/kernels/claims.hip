@@ -142,12 +142,13 @@ __global__ void __launch_bounds__(kBlock) k_claims_select(const uint8_t* __restr
 // jobs[i].flags; the lanes of a wave may hold different profiles, which only
 // makes the base of the LDS reads per-lane (their addresses depend on the lane's
 // position in its value already).  M is the scan's mode; the records are
-// written as above.
-template <int M>
-__device__ __forceinline__ void claims_each_body(Profiles& T, Select* S, const uint8_t* __restrict__ arena,
+// written as above.  SL is what a selecting mode selects by: Select's names or,
+// for kPath, Paths.
+template <int M, class SL>
+__device__ __forceinline__ void claims_each_body(Profiles& T, SL* S, const uint8_t* __restrict__ arena,
                                                  const jg_cjob* __restrict__ jobs, int64_t n,
                                                  const Profiles* __restrict__ table,
-                                                 const Select* __restrict__ select, uint8_t* __restrict__ code_out,
+                                                 const SL* __restrict__ select, uint8_t* __restrict__ code_out,
                                                  jg_claims* __restrict__ vals_out, jg_selected* __restrict__ sel_out) {
   static_assert(offsetof(Profiles, h) == 8 && sizeof(ProfileHeader) % 4 == 0 && offsetof(Profiles, pool) % 4 == 0,
                 "the table is copied by words");
@@ -162,10 +163,11 @@ __device__ __forceinline__ void claims_each_body(Profiles& T, Select* S, const u
     constexpr uint32_t pw0 = offsetof(Profiles, pool) / 4u;
     const uint32_t pw = (used + 3u) / 4u;
     for (uint32_t k = threadIdx.x; k < pw; k += kBlock) dst[pw0 + k] = src[pw0 + k];
-    if constexpr (M == kSelect) {
+    if constexpr (M >= kSelect) {
+      static_assert(sizeof(SL) % 4 == 0, "the names are copied by words");
       const uint32_t* ssrc = (const uint32_t*)select;
       uint32_t* sdst = (uint32_t*)S;
-      for (uint32_t k = threadIdx.x; k < sizeof(Select) / 4; k += kBlock) sdst[k] = ssrc[k];
+      for (uint32_t k = threadIdx.x; k < sizeof(SL) / 4; k += kBlock) sdst[k] = ssrc[k];
     }
   }
   __syncthreads();
@@ -182,14 +184,15 @@ __device__ __forceinline__ void claims_each_body(Profiles& T, Select* S, const u
   } else {
     jg_claims v;
     jg_selected q;
-    if constexpr (M == kSelect) code_out[i] = claims_select_each(src, J.len, T, p, *S, &v, &q);
+    if constexpr (M == kPath) code_out[i] = claims_paths_each(src, J.len, T, p, *S, &v, &q);
+    else if constexpr (M == kSelect) code_out[i] = claims_select_each(src, J.len, T, p, *S, &v, &q);
     else code_out[i] = claims_extract_each(src, J.len, T, p, &v);
     uint4* o = (uint4*)(vals_out + i);
     o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
     o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
     o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
     o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
-    if constexpr (M == kSelect) {
+    if constexpr (M >= kSelect) {
       uint4* t = (uint4*)(sel_out + i);
       t[0] = make_uint4(q.off[0], q.off[1], q.off[2], q.off[3]);
       t[1] = make_uint4(q.off[4], q.off[5], q.off[6], q.off[7]);
@@ -206,7 +209,7 @@ __global__ void __launch_bounds__(kBlock) k_claims_scan_each(const uint8_t* __re
                                                              const Profiles* __restrict__ table,
                                                              uint8_t* __restrict__ code_out) {
   __shared__ Profiles T;
-  claims_each_body<kVerdict>(T, nullptr, arena, jobs, n, table, nullptr, code_out, nullptr, nullptr);
+  claims_each_body<kVerdict, Select>(T, nullptr, arena, jobs, n, table, nullptr, code_out, nullptr, nullptr);
 }
 
 __global__ void __launch_bounds__(kBlock) k_claims_extract_each(const uint8_t* __restrict__ arena,
@@ -215,7 +218,7 @@ __global__ void __launch_bounds__(kBlock) k_claims_extract_each(const uint8_t* _
                                                                 uint8_t* __restrict__ code_out,
                                                                 jg_claims* __restrict__ vals_out) {
   __shared__ Profiles T;
-  claims_each_body<kExtract>(T, nullptr, arena, jobs, n, table, nullptr, code_out, vals_out, nullptr);
+  claims_each_body<kExtract, Select>(T, nullptr, arena, jobs, n, table, nullptr, code_out, vals_out, nullptr);
 }
 
 __global__ void __launch_bounds__(kBlock) k_claims_select_each(const uint8_t* __restrict__ arena,
@@ -227,7 +230,22 @@ __global__ void __launch_bounds__(kBlock) k_claims_select_each(const uint8_t* __
                                                                jg_selected* __restrict__ sel_out) {
   __shared__ Profiles T;
   __shared__ Select S;
-  claims_each_body<kSelect>(T, &S, arena, jobs, n, table, select, code_out, vals_out, sel_out);
+  claims_each_body<kSelect, Select>(T, &S, arena, jobs, n, table, select, code_out, vals_out, sel_out);
+}
+
+// k_claims_select_each for members named by path (jg_claims_paths): the resolved
+// paths sit in LDS beside the table, and a key at depth d <= JG_PATH_MAX_COMP is
+// compared from there with component d of the paths matched that far.
+__global__ void __launch_bounds__(kBlock) k_claims_paths_each(const uint8_t* __restrict__ arena,
+                                                              const jg_cjob* __restrict__ jobs, int64_t n,
+                                                              const Profiles* __restrict__ table,
+                                                              const Paths* __restrict__ paths,
+                                                              uint8_t* __restrict__ code_out,
+                                                              jg_claims* __restrict__ vals_out,
+                                                              jg_selected* __restrict__ sel_out) {
+  __shared__ Profiles T;
+  __shared__ Paths P;
+  claims_each_body<kPath, Paths>(T, &P, arena, jobs, n, table, paths, code_out, vals_out, sel_out);
 }
 
 }  // namespace
@@ -244,6 +262,14 @@ void launch_claims_each(const uint8_t* arena, const jg_cjob* jobs, int64_t n, co
     hipLaunchKernelGGL(k_claims_extract_each, grid, block, 0, s, arena, jobs, n, table, code_out, vals_out);
   else
     hipLaunchKernelGGL(k_claims_scan_each, grid, block, 0, s, arena, jobs, n, table, code_out);
+}
+
+void launch_claims_paths(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Profiles* table,
+                         const Paths* paths, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
+                         hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_claims_paths_each, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs,
+                     n, table, paths, code_out, vals_out, sel_out);
 }
 
 void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,

@@ -31,6 +31,11 @@
 // narrowed per key byte and resolved at the closing quote; the value's first
 // byte latches the slot's offset and type, its end the length.
 //
+// claims_paths_each() is a fourth mode (ScanT<kPath>): claims_select's outputs
+// for members named by a path of up to JG_PATH_MAX_COMP keys (Paths, in LDS
+// beside the profile table): component j is matched at depth j inside the object
+// that components 1..j-1 opened.
+//
 // The expected side is a template parameter of the scan (EX: slen / sbyte / auds
 // and the window's edges).  Expect is one; ProfileRef, one profile of a
 // Profiles table picked per token, is the other: claims_decide_each,
@@ -230,6 +235,59 @@ inline bool resolve_select(const jg_select& x, Select* S) {
   return true;
 }
 
+// The caller's claim paths as the path-selecting scan reads them (a device
+// buffer copied to LDS beside the profile table).  Masks over the paths hold
+// path k at bit 2k, the position of its field in the scan's matched depths.
+struct Paths {
+  uint32_t n;
+  uint32_t ge[JG_PATH_MAX_COMP];                      // ge[d-1]: the paths with at least d components
+  uint8_t ncomp[JG_MAX_PATHS];
+  uint8_t len[JG_MAX_PATHS][JG_PATH_MAX_COMP];
+  uint16_t off[JG_MAX_PATHS][JG_PATH_MAX_COMP];       // into pool
+  uint8_t pool[JG_MAX_PATHS * JG_PATH_MAX_COMP * JG_SELECT_NAME_MAX];
+};
+static_assert(sizeof(Paths) == 4 + 16 + 8 + 32 + 64 + 2048, "no padding in the paths");
+static_assert(JG_MAX_PATHS == JG_MAX_SELECT && JG_PATH_MAX_COMP == 4, "a path per jg_selected slot, two bits of matched depth");
+
+// Fills *P from the ABI's jg_paths.  False: more than JG_MAX_PATHS paths, a path
+// of no or more than JG_PATH_MAX_COMP components, a component resolve_select
+// refuses as a name, two equal paths.
+inline bool resolve_paths(const jg_paths& x, Paths* P) {
+  if (x.n > JG_MAX_PATHS) return false;
+  *P = Paths{};
+  uint32_t o = 0;
+  for (uint32_t k = 0; k < x.n; ++k) {
+    const uint32_t nc = x.ncomp[k];
+    if (nc == 0 || nc > JG_PATH_MAX_COMP || !x.names) return false;
+    P->ncomp[k] = (uint8_t)nc;
+    for (uint32_t d = 0; d < nc; ++d) {
+      const uint32_t l = x.comp_len[k][d];
+      if (l == 0 || l > JG_SELECT_NAME_MAX) return false;
+      P->len[k][d] = (uint8_t)l;
+      P->off[k][d] = (uint16_t)o;
+      for (uint32_t b = 0; b < l; ++b) {
+        const uint8_t c = x.names[o + b];
+        if (c < 0x20u || c > 0x7eu || c == '"' || c == '\\') return false;
+        P->pool[o + b] = c;
+      }
+      o += l;
+      P->ge[d] |= 1u << (2u * k);
+    }
+    for (uint32_t j = 0; j < k; ++j) {
+      if (P->ncomp[j] != nc) continue;
+      bool same = true;
+      for (uint32_t d = 0; d < nc && same; ++d) {
+        same = P->len[j][d] == P->len[k][d];
+        for (uint32_t b = 0; same && b < P->len[k][d]; ++b)
+          same = P->pool[P->off[j][d] + b] == P->pool[P->off[k][d] + b];
+      }
+      if (same) return false;
+    }
+  }
+  P->n = x.n;
+  return true;
+}
+
 enum : uint32_t {
   ST_START, ST_VALUE, ST_ARR_FIRST, ST_OBJ_FIRST, ST_OBJ_KEY, ST_COLON, ST_AFTER, ST_STR,
   ST_NUM_MINUS, ST_NUM_ZERO, ST_NUM_INT, ST_NUM_DOT, ST_NUM_FRAC, ST_LIT, ST_DONE
@@ -269,12 +327,26 @@ struct SelState {
 };
 struct ExtractSelect : Extract, SelState {};
 
+// What the path-selecting form (claims_paths_each) keeps beside those.  Selected
+// values nest here (a path may be a prefix of another), so the slot of the
+// member being read is kept per depth, and a slot is latched in two steps: its
+// offset and type when the value begins, its length when it ends.  kcand and
+// desc hold path k at bit 2k, as Paths::ge does.
+struct PathState {
+  uint32_t md = 0;                  // two bits per path: j = components 1..j matched, their objects still open
+  uint32_t desc = 0;                // paths whose next component is the key just read: they descend if its value is an object
+  uint32_t kselv = 0;               // four bits per depth 1..4: slot + 1 of that depth's member being read
+  uint32_t bv = 0;                  // this byte begins the values of these slots (bit 2k) at voff with type vtype
+};
+struct ExtractPath : Extract, SelState, PathState {};
+
 // The scan's compile-time modes: the verdict alone, with the jg_claims record,
 // and with the record and the caller's selected members (jg_selected)
-constexpr int kVerdict = 0, kExtract = 1, kSelect = 2;
+constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3;
 
 template <int M>
-struct ScanT : std::conditional_t<M == kSelect, ExtractSelect, std::conditional_t<M == kExtract, Extract, NoExtract>> {
+struct ScanT : std::conditional_t<M == kPath, ExtractPath, std::conditional_t<M == kSelect, ExtractSelect,
+                                  std::conditional_t<M == kExtract, Extract, NoExtract>>> {
   uint32_t st = ST_START;
   uint32_t depth = 0, stk = 0;      // open containers; bit d: container d+1 is an object
   uint32_t field = F_NONE;          // the top-level member whose value comes next
@@ -298,8 +370,22 @@ JG_CL_HD bool is_digit(uint32_t c) { return c - 0x30u < 10u; }
 // claims_select: the value of the selected depth-1 member (slot ksel - 1) begins
 // at decoded position `off` with jg_sel_type `type` (one such value is open at
 // a time: two scalars) ...
+// In a path scan the member is the one its depth's key selected, and the begin
+// is an event of its own for sel_commit: an outer selected object stays open
+// while an inner member is read, so nothing about it may live in these scalars.
+template <int M>
+JG_CL_HD uint32_t path_slot(const ScanT<M>& s) {      // slot + 1 of the member being read at this depth
+  return s.depth - 1u < 4u ? (s.kselv >> (4u * (s.depth - 1u))) & 0xfu : 0u;
+}
 template <int M>
 JG_CL_HD void sel_begin(ScanT<M>& s, uint32_t off, uint32_t type) {
+  if constexpr (M == kPath) {
+    const uint32_t slot = path_slot(s);
+    s.bv = slot ? 1u << (2u * (slot - 1u)) : 0u;
+    s.voff = off;
+    s.vtype = type;
+    return;
+  }
   if (s.depth != 1u || !s.ksel) return;
   s.voff = off;
   s.vtype = type;
@@ -308,6 +394,14 @@ JG_CL_HD void sel_begin(ScanT<M>& s, uint32_t off, uint32_t type) {
 // takes the quotes in (JG_SEL_STRING_RAW)
 template <int M>
 JG_CL_HD void sel_end(ScanT<M>& s, uint32_t end, uint32_t raw) {
+  if constexpr (M == kPath) {
+    s.ksel = path_slot(s);
+    if (!s.ksel) return;
+    s.kselv &= ~(0xfu << (4u * (s.depth - 1u)));      // the member is read: an array's elements at this depth have no key
+    s.ev = 1u + raw;
+    s.eva = end;
+    return;
+  }
   if (s.depth != 1u || !s.ksel) return;
   s.ev = 1u + raw;
   s.eva = end;
@@ -318,6 +412,30 @@ JG_CL_HD void sel_end(ScanT<M>& s, uint32_t end, uint32_t raw) {
 // registers more.  The last member of a name wins: its end overwrites the slot.
 template <int M>
 JG_CL_HD void sel_commit(ScanT<M>& s) {
+  if constexpr (M == kPath) {
+    // begin: off, -off, type; end: the length is end - off, and a raw string
+    // takes its quotes in.  Adds under selects: no slot is read by index.
+    if (s.bv) {
+      for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
+        const bool hit = (s.bv >> (2u * k)) & 1u;
+        s.soff[k] = hit ? s.voff : s.soff[k];
+        s.slen[k] = hit ? 0u - s.voff : s.slen[k];
+        s.stype = hit ? (s.stype & ~(0xfu << (4u * k))) | (s.vtype << (4u * k)) : s.stype;
+      }
+      s.bv = 0;
+    }
+    if (s.ev) {
+      const uint32_t raw = s.ev - 1u;
+      s.stype += raw << (4u * (s.ksel - 1u));                      // STRING + 1 = STRING_RAW
+      for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
+        const bool hit = s.ksel == k + 1u;
+        s.soff[k] = hit ? s.soff[k] - raw : s.soff[k];
+        s.slen[k] = hit ? s.slen[k] + s.eva + 2u * raw : s.slen[k];
+      }
+      s.ev = 0;
+    }
+    return;
+  }
   if (!s.ev) return;
   const uint32_t raw = s.ev - 1u, sh = 4u * (s.ksel - 1u);
   const uint32_t off = s.voff - raw, len = s.eva + raw - off;
@@ -346,7 +464,14 @@ JG_CL_HD void pop(ScanT<M>& s, uint32_t is_obj) {
   --s.depth;
   if constexpr (M >= kExtract) s.aud_len = s.depth == 1u && s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud's ]
   if (s.depth == 1u) s.aud_arr = 0;
-  if constexpr (M == kSelect) sel_end(s, s.dpos + 1u, 0u);        // the selected member's ] or }
+  if constexpr (M == kPath) {
+    // a matched object closed: the paths that were inside it (field == depth) are one component back
+    if (s.depth - 1u < 3u) {
+      const uint32_t x = s.md ^ (s.depth * 0x5555u);
+      s.md -= ~(x | (x >> 1)) & 0x5555u;
+    }
+  }
+  if constexpr (M >= kSelect) sel_end(s, s.dpos + 1u, 0u);        // the selected member's ] or }
   end_value(s);
 }
 
@@ -356,6 +481,10 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
   const uint32_t f = s.depth == 1u ? s.field : (uint32_t)F_NONE;
   const uint32_t elem = s.depth == 2u && s.aud_arr;        // an element of aud's array
   const uint32_t is_str3 = f - F_ISS < 3u, is_date = f - F_EXP < 3u;
+  if constexpr (M == kPath) {                          // only an object is descended into
+    s.md += c == '{' ? s.desc : 0u;
+    s.desc = 0;
+  }
   if (c == '"') {
     if (is_date) s.bad = 1;
     s.st = ST_STR;
@@ -374,13 +503,13 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
       s.aud_n = f == F_AUD ? 1u : s.aud_n + elem;
       s.present |= (is_str3 || f == F_AUD) ? 1u << f : 0u;
     }
-    if constexpr (M == kSelect) {
+    if constexpr (M >= kSelect) {
       s.hi = 0;
       sel_begin(s, s.dpos + 1u, (uint32_t)JG_SEL_STRING);
     }
   } else if (c == '{' || c == '[') {
     const uint32_t arr = c == '[';
-    if constexpr (M == kSelect) sel_begin(s, s.dpos, arr ? (uint32_t)JG_SEL_ARRAY : (uint32_t)JG_SEL_OBJECT);
+    if constexpr (M >= kSelect) sel_begin(s, s.dpos, arr ? (uint32_t)JG_SEL_ARRAY : (uint32_t)JG_SEL_OBJECT);
     if (arr && f == F_AUD) {
       s.aud_arr = 1;
       if constexpr (M >= kExtract) {
@@ -393,13 +522,13 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
   } else if (c == 't' || c == 'f' || c == 'n') {
     // null: skipped for iss/sub/jti, absent for a date; any literal elsewhere
     if ((f != F_NONE || elem) && !(c == 'n' && (is_str3 || is_date))) s.bad = 1;
-    if constexpr (M == kSelect)
+    if constexpr (M >= kSelect)
       sel_begin(s, s.dpos, c == 't' ? (uint32_t)JG_SEL_TRUE : c == 'f' ? (uint32_t)JG_SEL_FALSE : (uint32_t)JG_SEL_NULL);
     s.lit = c == 't' ? 0x657572u : c == 'f' ? 0x65736c61u : 0x6c6c75u;   // "rue" / "alse" / "ull"
     s.st = ST_LIT;
   } else if (c == '-' || is_digit(c)) {
     if (!is_date && (f != F_NONE || elem)) s.bad = 1;
-    if constexpr (M == kSelect) sel_begin(s, s.dpos, (uint32_t)JG_SEL_NUMBER);
+    if constexpr (M >= kSelect) sel_begin(s, s.dpos, (uint32_t)JG_SEL_NUMBER);
     s.isdate = is_date;
     s.nlen = 1;
     s.neg = c == '-';
@@ -425,12 +554,14 @@ JG_CL_HD void end_number(ScanT<M>& s) {
     s.iat = s.field == F_IAT ? v : s.iat;
     if constexpr (M >= kExtract) s.present |= 1u << s.field;
   }
-  if constexpr (M == kSelect) sel_end(s, s.dpos, 0u);              // dpos: the byte after the literal
+  if constexpr (M >= kSelect) sel_end(s, s.dpos, 0u);              // dpos: the byte after the literal
+  // this byte may go on to close the object around the number, itself selected by a shorter path
+  if constexpr (M == kPath) sel_commit(s);
   s.st = ST_AFTER;
 }
 
-template <int M, class EX>
-JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
+template <int M, class EX, class SL>
+JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
   (void)S;
   if (s.st >= ST_NUM_MINUS && s.st <= ST_NUM_FRAC) {
     const uint32_t d = is_digit(c);
@@ -473,6 +604,25 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
               s.ksel = slot;
             }
           }
+          if constexpr (M == kPath) {
+            // The survivors of this length are this key.  The path that ends here selects the
+            // member (equal paths are refused: at most one); a longer one descends if the value is
+            // an object, and its slot is ABSENT from here on: this member replaces an earlier one.
+            const uint32_t d = s.depth;
+            uint32_t m = s.kcand, slot = 0, desc = 0;
+            while (m) {
+              const uint32_t b = (uint32_t)__builtin_ctz(m), k = b >> 1;
+              m &= m - 1u;
+              const bool is = S->len[k][d - 1u] == s.klen, last = S->ncomp[k] == d;
+              slot = is && last ? k + 1u : slot;
+              desc |= is && !last ? 1u << b : 0u;
+            }
+            s.desc = desc;
+            if (d - 1u < 4u) s.kselv = (s.kselv & ~(0xfu << (4u * (d - 1u)))) | (slot << (4u * (d - 1u)));
+            s.bv = desc;                                        // sel_commit: ABSENT, as a value of type 0 at 0
+            s.voff = 0;
+            s.vtype = 0;
+          }
         } else {
           uint32_t m = s.cand, hit = 0;
           while (m) {
@@ -488,13 +638,13 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
             s.jti_len = s.cmpf == F_JTI ? s.pos : s.jti_len;
             s.aud_len = s.cmpf == F_AUD && !s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud as one string
           }
-          if constexpr (M == kSelect) sel_end(s, s.dpos, s.hi);
+          if constexpr (M >= kSelect) sel_end(s, s.dpos, s.hi);
           end_value(s);
         }
       } else {
         if (c < 0x20u || c == '\\') s.bad = 1;
         if (c >= 0x80u && s.ascii_only) s.bad = 1;
-        if constexpr (M == kSelect) s.hi |= c >= 0x80u;
+        if constexpr (M >= kSelect) s.hi |= c >= 0x80u;
         if (s.is_key) {
           if constexpr (M == kSelect) {                         // names still equal to the key so far
             uint32_t m = s.kcand;
@@ -502,6 +652,15 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
               const uint32_t k = (uint32_t)__builtin_ctz(m);
               m &= m - 1u;
               if (!(s.klen < S->len[k] && S->bytes[S->off[k] + s.klen] == c)) s.kcand &= ~(1u << k);
+            }
+          }
+          if constexpr (M == kPath) {                           // paths whose component at this depth still equals the key so far
+            uint32_t m = s.kcand;
+            while (m) {
+              const uint32_t b = (uint32_t)__builtin_ctz(m), k = b >> 1;
+              m &= m - 1u;
+              if (!(s.klen < S->len[k][s.depth - 1u] && S->pool[S->off[k][s.depth - 1u] + s.klen] == c))
+                s.kcand &= ~(1u << b);
             }
           }
           if (s.klen < 3u) s.kw = (s.kw << 8) | (c - 0x61u < 26u ? c - 0x20u : c);
@@ -520,7 +679,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
       if (c != (s.lit & 0xffu)) s.bad = 1;
       s.lit >>= 8;
       if (s.lit == 0) {
-        if constexpr (M == kSelect) sel_end(s, s.dpos + 1u, 0u);
+        if constexpr (M >= kSelect) sel_end(s, s.dpos + 1u, 0u);
         end_value(s);
       }
       break;
@@ -545,6 +704,10 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const Select* S) {
         s.kw = 0;
         s.cand = 0;
         if constexpr (M == kSelect) s.kcand = s.depth == 1u ? (1u << S->n) - 1u : 0u;
+        if constexpr (M == kPath) {                      // the paths that are matched down to the object this key is in
+          const uint32_t x = s.md ^ ((s.depth - 1u) * 0x5555u);
+          s.kcand = s.depth - 1u < 4u ? ~(x | (x >> 1)) & S->ge[s.depth - 1u] : 0u;
+        }
       } else if (c == '}' && s.st == ST_OBJ_FIRST) {
         pop(s, 1u);
       } else if (!is_ws(c)) {
@@ -606,11 +769,11 @@ JG_CL_HD uint8_t verdict(const ScanT<M>& s, const EX& E) {
 // The scan of one segment: claims_decide's code and, with X, the record.  The
 // state is a local of this function (handing it in by reference costs the
 // verdict-only kernel a third of its registers again).
-template <int M, class Src, class EX>
-JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* out, const Select* S = nullptr,
+template <int M, class Src, class EX, class SL = Select>
+JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* out, const SL* S = nullptr,
                               jg_selected* sel = nullptr) {
   if constexpr (M >= kExtract) *out = jg_claims{};                 // JG_CL_HOST: every byte zero
-  if constexpr (M == kSelect) *sel = jg_selected{};
+  if constexpr (M >= kSelect) *sel = jg_selected{};
   if ((len & 3u) == 1u) return JG_CL_HOST;
   ScanT<M> s;
   const uint32_t groups = (len + 3u) >> 2;
@@ -627,7 +790,7 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
     for (uint32_t k = 0; k < nb; ++k) {
       if constexpr (M >= kExtract) s.dpos = 3u * g + k;
       step(s, (trip >> 16) & 0xffu, E, S);
-      if constexpr (M == kSelect) sel_commit(s);
+      if constexpr (M >= kSelect) sel_commit(s);
       trip <<= 8;
     }
   }
@@ -647,7 +810,7 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
     out->aud_n = s.aud_n;
     out->present = s.present;
   }
-  if constexpr (M == kSelect) {
+  if constexpr (M >= kSelect) {
     for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
       sel->off[k] = s.soff[k];
       sel->len[k] = s.slen[k];
@@ -702,6 +865,19 @@ JG_CL_HD uint8_t claims_select_each(Src& src, uint32_t len, const Profiles& T, u
   return scan_segment<kSelect>(src, len, E, out, &S, sel);
 }
 
+// claims_extract_each's code and record for the same input, always, and the
+// members the caller's paths reach (include/jg.h jg_claims_paths): slot k
+// describes, as claims_select describes a top-level member, the value found by
+// taking, component by component, the last member of that name in the object
+// reached so far; ABSENT where a component is missing or what it names is not an
+// object.  Filled for every code other than JG_CL_HOST, all zero for JG_CL_HOST.
+template <class Src>
+JG_CL_HD uint8_t claims_paths_each(Src& src, uint32_t len, const Profiles& T, uint32_t p, const Paths& P,
+                                   jg_claims* out, jg_selected* sel) {
+  const ProfileRef E{T, p};
+  return scan_segment<kPath>(src, len, E, out, &P, sel);
+}
+
 }  // namespace jgclaims
 
 #if defined(__HIPCC__)
@@ -722,4 +898,9 @@ void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, 
 void launch_claims_each(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Profiles* table,
                         const jgclaims::Select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
                         hipStream_t s);
+// k_claims_paths_each: launch_claims_each's selecting form with `paths` (a device jgclaims::Paths)
+// in the place of the names
+void launch_claims_paths(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Profiles* table,
+                         const jgclaims::Paths* paths, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
+                         hipStream_t s);
 #endif

@@ -157,6 +157,32 @@ class Expected:
         return e
 
 
+class Path(tuple):
+    """A claim inside objects, by the keys that lead to it: Path("realm_access",
+    "roles") is claims["realm_access"]["roles"].  An element of the `names` of
+    SelectBatch / SelectBlob and their *Each forms.  Every component is a literal
+    key (str): nothing in it is parsed as a separator, and "a.b" stays one key."""
+
+    def __new__(cls, *components):
+        if not components:
+            raise ValueError("Path: at least one component")
+        for c in components:
+            if not isinstance(c, str):
+                raise TypeError("Path: components are str")
+        return super().__new__(cls, components)
+
+    def __repr__(self):
+        return "Path(" + ", ".join(repr(c) for c in self) + ")"
+
+
+def _paths_of(names):
+    """None for a list of names alone; else every element as a path (a name is a path of one component)"""
+    names = list(names)
+    if not any(isinstance(x, Path) for x in names):
+        return names, None
+    return names, [list(x) if isinstance(x, Path) else [x] for x in names]
+
+
 class Validator:
     """jwt.Validator (jwt/jwt.go:20-33)."""
 
@@ -229,11 +255,29 @@ class Validator:
         scan does not take (more than 8 distinct names, a name that is empty, over 64
         bytes, or not printable ASCII without quote and backslash) still answers,
         from the host path.  A name with a NUL raises ValueError.  `stats` as in
-        CheckBatch."""
-        rows, scanned, host = self._impl.select_batch(list(tokens), list(names), (expected or Expected())._native())
+        CheckBatch.
+
+        An element of `names` may be a Path: its value is what walking the claims map
+        along it reaches -- every value on the way must be an object holding the next
+        key, else the claim is absent; arrays are never descended.  The scan matches
+        component j at depth j inside the objects the earlier components opened (up to
+        8 distinct paths of up to 4 components; any other list still answers, from
+        the host path).  In `values` the key is the element as given, str or Path.  A
+        list of names alone makes exactly the call it made before."""
+        names, paths = _paths_of(names)
+        if paths is None:
+            rows, scanned, host = self._impl.select_batch(list(tokens), names, (expected or Expected())._native())
+        else:
+            rows, scanned, host = self._impl.select_paths_batch(list(tokens), paths, (expected or Expected())._native())
+            rows = self._keyed(rows, names)
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return rows
+
+    @staticmethod
+    def _keyed(rows, names):
+        """values by the path's index -> by the element of `names` as given"""
+        return [(c, None if v is None else {names[k]: x for k, x in v.items()}, e) for c, v, e in rows]
 
     def SelectBlob(self, blob: bytes, names: Sequence[str], expected: Expected = None, stats: dict = None) -> dict:
         """SelectBatch's throughput form: newline-separated tokens -> columns.
@@ -243,8 +287,13 @@ class Validator:
         for any string), "num" (n little-endian float64: a number's value, else 0),
         "text_off" (n + 1 little-endian uint32) and "text": a string's UTF-8 bytes,
         an array's or object's JSON as Go's json.Marshal writes it, empty otherwise.
-        The rows of a rejected token are empty.  `stats` as in CheckBatch."""
-        cols, scanned, host = self._impl.select_blob(blob, list(names), (expected or Expected())._native())
+        The rows of a rejected token are empty.  `stats` as in CheckBatch.  `names`
+        may hold Paths, as in SelectBatch: "sel" has one dict per element."""
+        names, paths = _paths_of(names)
+        if paths is None:
+            cols, scanned, host = self._impl.select_blob(blob, names, (expected or Expected())._native())
+        else:
+            cols, scanned, host = self._impl.select_paths_blob(blob, paths, (expected or Expected())._native())
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return cols
@@ -294,8 +343,14 @@ class Validator:
     def SelectBatchEach(self, tokens: Sequence, names: Sequence[str], expected: Sequence[Expected],
                         which: Sequence[int], stats: dict = None):
         """SelectBatch with expected[which[i]] for tokens[i]; one name list for the batch."""
-        rows, scanned, host = self._impl.select_batch_each(list(tokens), list(names), self._natives(expected),
-                                                           list(which))
+        names, paths = _paths_of(names)
+        if paths is None:
+            rows, scanned, host = self._impl.select_batch_each(list(tokens), names, self._natives(expected),
+                                                               list(which))
+        else:
+            rows, scanned, host = self._impl.select_paths_batch_each(list(tokens), paths, self._natives(expected),
+                                                                     list(which))
+            rows = self._keyed(rows, names)
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return rows
@@ -303,7 +358,11 @@ class Validator:
     def SelectBlobEach(self, blob: bytes, names: Sequence[str], expected: Sequence[Expected], which,
                        stats: dict = None) -> dict:
         """SelectBlob with expected[which[i]] for token i; `which` as in CheckBlobEach."""
-        cols, scanned, host = self._impl.select_blob_each(blob, list(names), self._natives(expected), which)
+        names, paths = _paths_of(names)
+        if paths is None:
+            cols, scanned, host = self._impl.select_blob_each(blob, names, self._natives(expected), which)
+        else:
+            cols, scanned, host = self._impl.select_paths_blob_each(blob, paths, self._natives(expected), which)
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return cols
@@ -317,4 +376,5 @@ def NewValidator(keyset: Optional[KeySet]):
 
 __all__ = ["RS256", "RS384", "RS512", "ES256", "ES384", "ES512", "PS256", "PS384", "PS512", "EdDSA",
            "DefaultLeewaySeconds", "PublicKey", "SupportedSigningAlgorithm", "ParsePublicKeyPEM", "KeySet",
-           "NewStaticKeySet", "NewJSONWebKeySet", "NewOIDCDiscoveryKeySet", "Expected", "Validator", "NewValidator"]
+           "NewStaticKeySet", "NewJSONWebKeySet", "NewOIDCDiscoveryKeySet", "Expected", "Path", "Validator",
+           "NewValidator"]

@@ -488,6 +488,52 @@ int jg_claims_each(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                    uint8_t* code_out, jg_claims* vals_out /* may be NULL */,
                    jg_selected* sel_out /* may be NULL */);
 
+/* ---- the selecting scan for claims inside objects ----
+ * jg_claims_each's selecting form for members that are not at the top level
+ * (Keycloak's realm_access.roles, the cnf.jkt of RFC 9449, the act.sub of RFC
+ * 8693): `paths` holds up to JG_MAX_PATHS paths of 1..JG_PATH_MAX_COMP
+ * components each, a component being a name under jg_select's rules, and slot k
+ * of sel_out[i] describes the value Go reaches in the claims map by walking
+ * path k:
+ *  - start at the top-level object; for each component, if the current value
+ *    is not an object the slot is JG_SEL_ABSENT, else take the LAST member whose
+ *    key equals the component byte for byte, or ABSENT if there is none: a
+ *    repeated parent replaces the earlier one wholesale ({"a":{"b":1},"a":{}}
+ *    is ABSENT for a/b), arrays are never descended, and component j only
+ *    matches a key at depth j;
+ *  - the value reached after the last component is described exactly as
+ *    jg_claims_select describes a top-level member: the same jg_sel_type, the
+ *    same spans, null is NULL.  A one-component path is jg_claims_select's slot
+ *    for that name, byte for byte.
+ * Paths may share a prefix, and one may be a prefix of another (a -> the
+ * OBJECT's span, a/b -> its member).  Components are literal keys: no
+ * separator is parsed, "a.b" is one component.
+ * Selecting by path never changes a decision: code_out and vals_out are
+ * jg_claims_each's for the same jobs and profiles, byte for byte, and no payload
+ * is JG_CL_HOST because of `paths` (a payload with a backslash is HOST already; a
+ * nested key with a byte >= 0x80 is not, and equals no component).  For
+ * JG_CL_HOST all 80 bytes of sel_out[i] are zero; for every other code it is
+ * filled; with paths->n == 0 every slot is ABSENT.
+ * jobs[i].flags is the profile index.  Everything else is jg_claims_each's:
+ * blocking, first device, the scan's stream and lock, kept buffers (one more for
+ * the resolved paths, uploaded whole per call), -2 on an infrastructure error,
+ * njobs == 0 returns 0.  -1: everything jg_claims_each refuses; paths->n over
+ * JG_MAX_PATHS; an ncomp of 0 or over JG_PATH_MAX_COMP; a component jg_select
+ * would refuse as a name; two equal paths; paths, vals_out or sel_out NULL with
+ * njobs > 0. */
+#define JG_MAX_PATHS 8
+#define JG_PATH_MAX_COMP 4
+typedef struct jg_paths {
+  const uint8_t* names;                      /* components back to back, path by path */
+  uint32_t n;                                /* 0..JG_MAX_PATHS */
+  uint32_t ncomp[JG_MAX_PATHS];              /* 1..JG_PATH_MAX_COMP */
+  uint32_t comp_len[JG_MAX_PATHS][JG_PATH_MAX_COMP];
+} jg_paths;
+int jg_claims_paths(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                    const jg_cjob* jobs, size_t njobs,
+                    const jg_expect* expects, uint32_t nexpect, const jg_paths* paths,
+                    uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 
