@@ -16,13 +16,16 @@ ALG_IDS = {"RS256": 1, "RS384": 2, "RS512": 3, "PS256": 4, "PS384": 5, "PS512": 
            "ES256": 7, "ES384": 8, "ES512": 9, "EdDSA": 10}
 KEY_RSA, KEY_EC, KEY_ED25519 = 1, 2, 3
 CURVE_IDS = {"P-256": 1, "P-384": 2, "P-521": 3}
+# jg_debug_table_read: the fixed-base tables (JG_TABLE_*), and what Context.table_read pre-fills its buffer with
+TABLE_P256_G, TABLE_P384_G, TABLE_P521_G, TABLE_ED25519_B = -1, -2, -3, -4
+TABLE_READ_FILL = 0xA5A5A5A5
 
 # every symbol include/jg.h declares
 EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_last_error",
            "jg_host_alloc", "jg_host_free", "jg_batch_stage", "jg_batch_run", "jg_batch_enqueue", "jg_batch_sync",
            "jg_batch_free", "jg_batch_kernel_times", "jg_batch_exceptions", "jg_hash_batch", "jg_version",
            "jg_submit", "jg_wait", "jg_set_chunk", "jg_set_zero_copy", "jg_set_table_budget", "jg_keys_wait_tables",
-           "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest",
+           "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest", "jg_debug_table_read",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
            "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
            "jg_claims_paths"]
@@ -170,6 +173,8 @@ def lib():
         L.jg_debug_lifetime_check.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
                                               ctypes.POINTER(ctypes.c_uint64)]
         L.jg_debug_table_digest.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+        L.jg_debug_table_read.argtypes = [vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, vp, sz] + \
+            [ctypes.POINTER(ctypes.c_int)] * 4
         L.jg_debug_tables_built.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.jg_debug_small_path.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         L.jg_version.restype = ctypes.c_char_p
@@ -297,6 +302,29 @@ class Context:
         if lib().jg_debug_table_digest(self.h, int(key), ctypes.byref(v)) != 0:
             raise JgError(f"jg_debug_table_digest: {self.error()}")
         return v.value
+
+    def table_read(self, key, first_entry=0, n_entries=0, out_words=None):
+        """jg_debug_table_read: raw words of n_entries comb-table entries of key
+        `key` (or of a fixed-base table: TABLE_P256_G .. TABLE_ED25519_B) from
+        entry first_entry on.  Returns (words, cls, width, nwin, stride_words);
+        n_entries = 0 reads the geometry alone.  out_words: the buffer's size
+        in words when it is to differ from what the entries need.  Raises
+        JgError where the hook refuses; the error's `words` holds the buffer,
+        which the hook then left untouched."""
+        geo = [ctypes.c_int(0) for _ in range(4)]
+        refs = [ctypes.byref(g) for g in geo]
+        L = lib()
+        if out_words is None:
+            if L.jg_debug_table_read(self.h, int(key), 0, 0, None, 0, *refs) != 0:
+                raise JgError(f"jg_debug_table_read: {self.error()}")
+            out_words = int(n_entries) * geo[3].value
+        buf = (ctypes.c_uint32 * max(1, int(out_words)))(*([TABLE_READ_FILL] * max(1, int(out_words))))
+        rc = L.jg_debug_table_read(self.h, int(key), int(first_entry), int(n_entries), buf, int(out_words), *refs)
+        if rc != 0:
+            e = JgError(f"jg_debug_table_read rc={rc}: {self.error()}")
+            e.words = list(buf)
+            raise e
+        return (list(buf[:int(n_entries) * geo[3].value]),) + tuple(g.value for g in geo)
 
     def tables_built(self):
         """jg_debug_tables_built: comb tables this context has built (cache reuses excluded)."""

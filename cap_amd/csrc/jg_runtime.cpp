@@ -3098,6 +3098,70 @@ int jg_debug_table_digest(jg_ctx* ctx, int key, uint64_t* digest) {
   }
 }
 
+int jg_debug_table_read(jg_ctx* ctx, int key, uint64_t first_entry, uint32_t n_entries, uint32_t* out,
+                        size_t out_words, int* cls, int* width, int* nwin, int* stride_words) {
+  if (!ctx) return -1;
+  try {
+    // key loads publish generations and build the fixed-base tables under this lock
+    std::lock_guard<std::mutex> lg(ctx->load_mu);
+    KeyStateP ks = ctx->state();
+    if (ctx->devs.empty()) { ctx->set_err("jg_debug_table_read: no device"); return -1; }
+    Device* d = ctx->devs[0].get();
+    int c = 0, w = 0;
+    const uint32_t* tab = nullptr;
+    if (key >= 0) {
+      if (!ks || key >= (int)ks->keys.size() || ks->dev.empty()) {
+        ctx->set_err("jg_debug_table_read: no key " + std::to_string(key));
+        return -1;
+      }
+      const DevGen& G = *ks->dev[0];
+      c = ks->keys[(size_t)key].cls;
+      w = G.kw[(size_t)key];
+      tab = (const uint32_t*)(uintptr_t)G.mirror[(size_t)key].tab;
+      if (w == 0 || !tab) {
+        ctx->set_err("jg_debug_table_read: key " + std::to_string(key) + " has no comb table");
+        return -1;
+      }
+    } else {
+      c = key == JG_TABLE_P256_G ? CLS_P256 : key == JG_TABLE_P384_G ? CLS_P384 : key == JG_TABLE_P521_G ? CLS_P521
+          : key == JG_TABLE_ED25519_B ? CLS_ED25519 : -1;
+      if (c < 0) { ctx->set_err("jg_debug_table_read: no table " + std::to_string(key)); return -1; }
+      tab = c == CLS_ED25519 ? d->btab : d->gtab[c];
+      w = c == CLS_ED25519 ? ed_comb_w(true) : ec_comb_w(c, true);
+      if (!tab) {
+        ctx->set_err(std::string("jg_debug_table_read: the ") + cls_name(c) + " fixed-base table is not built yet");
+        return -1;
+      }
+    }
+    const uint64_t stride = c == CLS_ED25519 ? (uint64_t)ED_STRIDE : (uint64_t)ec_stride(c);
+    const uint64_t nw = c == CLS_ED25519 ? (uint64_t)ed_windows_w(w) : (uint64_t)ec_windows_w(c, w);
+    const uint64_t total = nw << (w - 1);
+    if (cls) *cls = c;
+    if (width) *width = w;
+    if (nwin) *nwin = (int)nw;
+    if (stride_words) *stride_words = (int)stride;
+    if (first_entry > total || n_entries > total - first_entry) {
+      ctx->set_err("jg_debug_table_read: entries " + std::to_string(first_entry) + " + " + std::to_string(n_entries) +
+                   " pass the table's " + std::to_string(total));
+      return -1;
+    }
+    if ((uint64_t)n_entries * stride > out_words || (n_entries > 0 && !out)) {
+      ctx->set_err("jg_debug_table_read: " + std::to_string((uint64_t)n_entries * stride) + " words do not fit out_words = " +
+                   std::to_string(out_words));
+      return -1;
+    }
+    if (n_entries == 0) return 0;
+    HIPCHK(hipSetDevice(d->id));
+    HIPCHK(hipMemcpyAsync(out, tab + first_entry * stride, sizeof(uint32_t) * n_entries * stride, hipMemcpyDeviceToHost,
+                          d->kstream));
+    HIPCHK(hipStreamSynchronize(d->kstream));
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(e.what());
+    return -2;
+  }
+}
+
 int jg_debug_tables_built(jg_ctx* ctx, uint64_t* built) {
   if (!ctx || !built) return -1;
   *built = ctx->tables_built.load();

@@ -159,6 +159,36 @@ int jg_debug_lifetime_check(int enable, uint64_t* violations, uint64_t* checked)
  * different paths must agree.  Returns 0, -1 or -2. */
 int jg_debug_table_digest(jg_ctx* ctx, int key, uint64_t* digest);
 
+/* Test hook: read raw comb-table entries back from the first device.  key >= 0
+ * selects that key's current table; a negative key one of the fixed-base
+ * tables every token of a curve reads: JG_TABLE_P256_G, JG_TABLE_P384_G,
+ * JG_TABLE_P521_G (the curve generators) or JG_TABLE_ED25519_B (the Ed25519
+ * base point), which exist once a key of the curve has been loaded.  A table
+ * of comb width W holds nwin windows of NE = 2^(W-1) entries; entry
+ * e = w * NE + (d - 1) is d * 2^(W w) * P (P: the key's point, the generator,
+ * or for an Ed25519 key -A), `stride_words` 32-bit words each:
+ *   P-256          x then y, 8 little-endian 32-bit words each, canonical
+ *                  Montgomery form with R = 2^280 (stride 16);
+ *   P-384, P-521   x then y, L = 15 / 20 limbs of 28 bits each, canonical
+ *                  Montgomery form with R = 2^(28 L) (stride 32 / 40);
+ *   Ed25519        y + x, y - x, 2 d x y: three canonical values of 10
+ *                  radix-2^25.5 limbs each (stride 32).
+ * Words of the stride past these are padding.  The call copies n_entries
+ * entries from first_entry on into out (out_words: its capacity in words) and
+ * stores the table's class (the kernel class: 4 P-256, 5 P-384, 6 P-521, 7
+ * Ed25519), comb width, window count and stride through the last four
+ * pointers (each may be NULL; written whenever the table exists, also when
+ * the range is refused).  Returns 0; -1 with jg_last_error set and nothing
+ * copied for a key out of range or without a table (RSA, invalid), a
+ * fixed-base table not built yet, a range past nwin * NE, or out_words too
+ * small; -2 on an infrastructure error. */
+#define JG_TABLE_P256_G (-1)
+#define JG_TABLE_P384_G (-2)
+#define JG_TABLE_P521_G (-3)
+#define JG_TABLE_ED25519_B (-4)
+int jg_debug_table_read(jg_ctx* ctx, int key, uint64_t first_entry, uint32_t n_entries, uint32_t* out,
+                        size_t out_words, int* cls, int* width, int* nwin, int* stride_words);
+
 /* Test hook: the number of key comb tables this context has built so far, on
  * every device (key loads and background width upgrades; a table reused from
  * the per-device cache -- same key content and width -- is not a build).

@@ -4,8 +4,10 @@
   signed comb digits select the LAST entry of a window (|d| = 2^(W-1)), which
   uniformly random digits reach with probability ~2^-W per window; every one
   must verify at the fixture's key widths.
-- A table widened by the background upgrader equals the table a synchronous
-  build gives (jg_debug_table_digest), key by key, for the golden keys.
+- A table widened by the background upgrader while batches run equals the
+  table the upgrader builds on an idle device (jg_debug_table_digest), key by
+  key, for the golden keys.  Both are sliced upgrader builds: the unsliced
+  build and an independent reference are tests/test_gpu_table_exact.py's.
 """
 import json
 import os
@@ -44,8 +46,10 @@ def test_edge_digit_tokens_verify():
 
 
 def test_background_widening_matches_sync_build():
-    """Context A widens its tables while golden-token batches run against it;
-    context B widens the same keys with nothing else running."""
+    """Busy against idle upgrader builds: context A widens its tables while
+    golden-token batches run against it; context B widens the same keys with
+    nothing else running.  Neither side is a synchronous (CAPJWT_TABLES_SYNC)
+    build -- both go through the background upgrader and are sliced."""
     from cap_amd import _lib
     keys, toks = H.golden()
     kid_index = {k["kid"]: i for i, k in enumerate(keys)}
