@@ -118,6 +118,83 @@ class JgPaths(ctypes.Structure):
     _fields_ = [("names", ctypes.c_void_p), ("n", ctypes.c_uint32), ("ncomp", ctypes.c_uint32 * MAX_PATHS),
                 ("comp_len", (ctypes.c_uint32 * PATH_MAX_COMP) * MAX_PATHS)]
 
+
+def _cjobs(rows):
+    """(off, len, flags) rows -> a JgCJob array (of one unused job for no rows)"""
+    rows = list(rows)
+    cj = (JgCJob * max(1, len(rows)))()
+    for j, (off, ln, flags) in zip(cj, rows):
+        j.off, j.len, j.flags = off, ln, flags
+    return cj
+
+
+def _jg_expect(d, e=None):
+    """An Expected dict (Context.claims_scan) -> (JgExpect, the buffer its strs points into:
+    to be kept alive).  `e`: the JgExpect to fill."""
+    e = JgExpect() if e is None else e
+    auds = [bytes(a) for a in d.get("audiences", [])]
+    strs = [bytes(d.get(k, b"")) for k in ("issuer", "subject", "id")]
+    blob = b"".join(strs + auds)
+    keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+    e.strs = ctypes.cast(keep, ctypes.c_void_p)
+    e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
+    e.naud = len(auds)
+    for k, a in enumerate(auds[:MAX_AUD]):
+        e.aud_len[k] = len(a)
+    e.now_sec, e.now_nsec = int(d["now_sec"]), int(d["now_nsec"])
+    e.skew_ns = int(d["skew_ns"])
+    e.exp_leeway_s, e.nbf_leeway_s = int(d["exp_leeway_s"]), int(d["nbf_leeway_s"])
+    return e, keep
+
+
+def _jg_expects(ds):
+    """A list of Expected dicts -> (JgExpect array, the buffers to keep alive)"""
+    es = (JgExpect * max(1, len(ds)))()
+    return es, [_jg_expect(d, e)[1] for e, d in zip(es, ds)]
+
+
+def _jg_select(names):
+    """Claim names -> (JgSelect, the buffer to keep alive)"""
+    names = [bytes(x) for x in names]
+    blob = b"".join(names)
+    sel = JgSelect()
+    keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+    sel.names = ctypes.cast(keep, ctypes.c_void_p)
+    sel.n = len(names)
+    for k, x in enumerate(names[:MAX_SELECT]):
+        sel.name_len[k] = len(x)
+    return sel, keep
+
+
+def _jg_paths(paths):
+    """Claim paths, each a sequence of components -> (JgPaths, the buffer to keep alive)"""
+    paths = [[bytes(c) for c in path] for path in paths]
+    ps = JgPaths()
+    ps.n = len(paths)
+    blob = b""
+    for k, path in enumerate(paths[:MAX_PATHS]):
+        ps.ncomp[k] = len(path)
+        for d, c in enumerate(path[:PATH_MAX_COMP]):        # past what the struct holds the path is refused on its count
+            ps.comp_len[k][d] = len(c)
+            blob += c
+    keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+    ps.names = ctypes.cast(keep, ctypes.c_void_p)
+    return ps, keep
+
+
+def _poisoned(ctype, n):
+    """An output array of max(1, n) records, every byte 0xee"""
+    buf = (ctype * max(1, n))()
+    ctypes.memset(buf, 0xee, ctypes.sizeof(buf))
+    return buf
+
+
+def _records(ctype, buf, n):
+    """The first n records of an output array, copied out"""
+    return (ctype * n).from_buffer_copy(bytes(buf)[:ctypes.sizeof(ctype) * n])
+
+
+
 _lib = None
 
 
@@ -369,33 +446,22 @@ class Context:
             raise JgError(f"jg_verify_batch rc={rc}: {self.error()}")
         return bytes(out[:n])
 
+    def _claims_call(self, entry, arena_bytes, cj, n, *args):
+        buf = bytes(arena_bytes) or b"\0"
+        rc = getattr(lib(), entry)(self.h, buf, len(arena_bytes), cj, n, *args)
+        if rc != 0:
+            raise JgError(f"{entry} rc={rc}: {self.error()}")
+
     def claims_scan(self, arena_bytes, spans, expect, flags=0):
         """jg_claims_scan: one jg_claim_code byte per (off, len) span of base64url
         payload segment in `arena_bytes`.  `expect`: a dict with issuer, subject,
         id (bytes), audiences (list of bytes), now_sec, now_nsec, skew_ns,
         exp_leeway_s, nbf_leeway_s -- already resolved (see include/jg.h)."""
         n = len(spans)
-        jobs = (JgCJob * max(1, n))()
-        for i, (off, ln) in enumerate(spans):
-            jobs[i].off, jobs[i].len, jobs[i].flags = off, ln, flags
-        auds = [bytes(a) for a in expect.get("audiences", [])]
-        strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
-        blob = b"".join(strs + auds)
-        e = JgExpect()
-        keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
-        e.strs = ctypes.cast(keep, ctypes.c_void_p)
-        e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
-        e.naud = len(auds)
-        for k, a in enumerate(auds[:MAX_AUD]):
-            e.aud_len[k] = len(a)
-        e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
-        e.skew_ns = int(expect["skew_ns"])
-        e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
-        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
-        buf = bytes(arena_bytes) or b"\0"
-        rc = lib().jg_claims_scan(self.h, buf, len(arena_bytes), jobs, n, ctypes.byref(e), out)
-        if rc != 0:
-            raise JgError(f"jg_claims_scan rc={rc}: {self.error()}")
+        e, _keep = _jg_expect(expect)
+        out = _poisoned(ctypes.c_char, n)
+        self._claims_call("jg_claims_scan", arena_bytes, _cjobs((o, ln, flags) for o, ln in spans), n,
+                          ctypes.byref(e), out)
         return out.raw[:n]
 
     def claims_extract(self, arena_bytes, spans, expect, flags=0):
@@ -403,31 +469,11 @@ class Context:
         record of the registered claims -> (codes: bytes, vals: JgClaims array).
         Both outputs are poisoned with 0xee before the call."""
         n = len(spans)
-        jobs = (JgCJob * max(1, n))()
-        for i, (off, ln) in enumerate(spans):
-            jobs[i].off, jobs[i].len, jobs[i].flags = off, ln, flags
-        auds = [bytes(a) for a in expect.get("audiences", [])]
-        strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
-        blob = b"".join(strs + auds)
-        e = JgExpect()
-        keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
-        e.strs = ctypes.cast(keep, ctypes.c_void_p)
-        e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
-        e.naud = len(auds)
-        for k, a in enumerate(auds[:MAX_AUD]):
-            e.aud_len[k] = len(a)
-        e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
-        e.skew_ns = int(expect["skew_ns"])
-        e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
-        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
-        vals = (JgClaims * max(1, n))()
-        ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
-        buf = bytes(arena_bytes) or b"\0"
-        rc = lib().jg_claims_extract(self.h, buf, len(arena_bytes), jobs, n, ctypes.byref(e), out,
-                                     ctypes.cast(vals, ctypes.c_void_p))
-        if rc != 0:
-            raise JgError(f"jg_claims_extract rc={rc}: {self.error()}")
-        return out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n])
+        e, _keep = _jg_expect(expect)
+        out, vals = _poisoned(ctypes.c_char, n), _poisoned(JgClaims, n)
+        self._claims_call("jg_claims_extract", arena_bytes, _cjobs((o, ln, flags) for o, ln in spans), n,
+                          ctypes.byref(e), out, ctypes.cast(vals, ctypes.c_void_p))
+        return out.raw[:n], _records(JgClaims, vals, n)
 
     def claims_select(self, arena_bytes, spans, expect, names, flags=0):
         """jg_claims_select: claims_extract's codes and records and, per span, the
@@ -435,42 +481,13 @@ class Context:
         -> (codes: bytes, vals: JgClaims array, sels: JgSelected array).  All three
         outputs are poisoned with 0xee before the call."""
         n = len(spans)
-        jobs = (JgCJob * max(1, n))()
-        for i, (off, ln) in enumerate(spans):
-            jobs[i].off, jobs[i].len, jobs[i].flags = off, ln, flags
-        auds = [bytes(a) for a in expect.get("audiences", [])]
-        strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
-        blob = b"".join(strs + auds)
-        e = JgExpect()
-        keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
-        e.strs = ctypes.cast(keep, ctypes.c_void_p)
-        e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
-        e.naud = len(auds)
-        for k, a in enumerate(auds[:MAX_AUD]):
-            e.aud_len[k] = len(a)
-        e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
-        e.skew_ns = int(expect["skew_ns"])
-        e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
-        names = [bytes(x) for x in names]
-        nblob = b"".join(names)
-        sel = JgSelect()
-        nkeep = ctypes.create_string_buffer(nblob, max(1, len(nblob)))
-        sel.names = ctypes.cast(nkeep, ctypes.c_void_p)
-        sel.n = len(names)
-        for k, x in enumerate(names[:MAX_SELECT]):
-            sel.name_len[k] = len(x)
-        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
-        vals = (JgClaims * max(1, n))()
-        ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
-        sels = (JgSelected * max(1, n))()
-        ctypes.memset(sels, 0xee, ctypes.sizeof(sels))
-        buf = bytes(arena_bytes) or b"\0"
-        rc = lib().jg_claims_select(self.h, buf, len(arena_bytes), jobs, n, ctypes.byref(e), ctypes.byref(sel), out,
-                                    ctypes.cast(vals, ctypes.c_void_p), ctypes.cast(sels, ctypes.c_void_p))
-        if rc != 0:
-            raise JgError(f"jg_claims_select rc={rc}: {self.error()}")
-        return (out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n]),
-                (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n]))
+        e, _keep = _jg_expect(expect)
+        sel, _nkeep = _jg_select(names)
+        out, vals, sels = _poisoned(ctypes.c_char, n), _poisoned(JgClaims, n), _poisoned(JgSelected, n)
+        self._claims_call("jg_claims_select", arena_bytes, _cjobs((o, ln, flags) for o, ln in spans), n,
+                          ctypes.byref(e), ctypes.byref(sel), out, ctypes.cast(vals, ctypes.c_void_p),
+                          ctypes.cast(sels, ctypes.c_void_p))
+        return out.raw[:n], _records(JgClaims, vals, n), _records(JgSelected, sels, n)
 
     def claims_each(self, arena_bytes, jobs, expects, mode="scan", names=None, nexpect=None):
         """jg_claims_each: the three scans with a profile per job.  `jobs`: (off,
@@ -480,58 +497,23 @@ class Context:
         return them.  The outputs are poisoned with 0xee before the call.
         `nexpect` overrides the count passed to the ABI (for its argument checks)."""
         n = len(jobs)
-        cj = (JgCJob * max(1, n))()
-        for i, (off, ln, prof) in enumerate(jobs):
-            cj[i].off, cj[i].len, cj[i].flags = off, ln, prof
-        es = (JgExpect * max(1, len(expects)))()
-        keep = []
-        for e, expect in zip(es, expects):
-            auds = [bytes(a) for a in expect.get("audiences", [])]
-            strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
-            blob = b"".join(strs + auds)
-            keep.append(ctypes.create_string_buffer(blob, max(1, len(blob))))
-            e.strs = ctypes.cast(keep[-1], ctypes.c_void_p)
-            e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
-            e.naud = len(auds)
-            for k, a in enumerate(auds[:MAX_AUD]):
-                e.aud_len[k] = len(a)
-            e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
-            e.skew_ns = int(expect["skew_ns"])
-            e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
+        es, _keep = _jg_expects(expects)
         if mode not in ("scan", "extract", "select"):
             raise ValueError("mode: scan, extract or select")
-        sel = None
-        if names is not None:
-            names = [bytes(x) for x in names]
-            nblob = b"".join(names)
-            sel = JgSelect()
-            nkeep = ctypes.create_string_buffer(nblob, max(1, len(nblob)))
-            sel.names = ctypes.cast(nkeep, ctypes.c_void_p)
-            sel.n = len(names)
-            for k, x in enumerate(names[:MAX_SELECT]):
-                sel.name_len[k] = len(x)
-        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
-        vals = sels = None
-        if mode != "scan":
-            vals = (JgClaims * max(1, n))()
-            ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
-        if mode == "select":
-            sels = (JgSelected * max(1, n))()
-            ctypes.memset(sels, 0xee, ctypes.sizeof(sels))
-        buf = bytes(arena_bytes) or b"\0"
-        rc = lib().jg_claims_each(self.h, buf, len(arena_bytes), cj, n, es,
-                                  len(expects) if nexpect is None else nexpect,
-                                  ctypes.byref(sel) if sel is not None else None, out,
-                                  ctypes.cast(vals, ctypes.c_void_p) if vals is not None else None,
-                                  ctypes.cast(sels, ctypes.c_void_p) if sels is not None else None)
-        if rc != 0:
-            raise JgError(f"jg_claims_each rc={rc}: {self.error()}")
+        sel, _nkeep = _jg_select(names) if names is not None else (None, None)
+        out = _poisoned(ctypes.c_char, n)
+        vals = _poisoned(JgClaims, n) if mode != "scan" else None
+        sels = _poisoned(JgSelected, n) if mode == "select" else None
+        self._claims_call("jg_claims_each", arena_bytes, _cjobs(jobs), n, es,
+                          len(expects) if nexpect is None else nexpect,
+                          ctypes.byref(sel) if sel is not None else None, out,
+                          ctypes.cast(vals, ctypes.c_void_p) if vals is not None else None,
+                          ctypes.cast(sels, ctypes.c_void_p) if sels is not None else None)
         if mode == "scan":
             return out.raw[:n]
-        v = (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n])
         if mode == "extract":
-            return out.raw[:n], v
-        return out.raw[:n], v, (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n])
+            return out.raw[:n], _records(JgClaims, vals, n)
+        return out.raw[:n], _records(JgClaims, vals, n), _records(JgSelected, sels, n)
 
     def claims_paths(self, arena_bytes, jobs, expects, paths, nexpect=None, null=()):
         """jg_claims_paths: claims_each's selecting form for members named by path.
@@ -542,50 +524,15 @@ class Context:
         the count passed to the ABI and `null` names arguments ("paths", "vals",
         "sels") to pass as NULL (both for its argument checks)."""
         n = len(jobs)
-        cj = (JgCJob * max(1, n))()
-        for i, (off, ln, prof) in enumerate(jobs):
-            cj[i].off, cj[i].len, cj[i].flags = off, ln, prof
-        es = (JgExpect * max(1, len(expects)))()
-        keep = []
-        for e, expect in zip(es, expects):
-            auds = [bytes(a) for a in expect.get("audiences", [])]
-            strs = [bytes(expect.get(k, b"")) for k in ("issuer", "subject", "id")]
-            blob = b"".join(strs + auds)
-            keep.append(ctypes.create_string_buffer(blob, max(1, len(blob))))
-            e.strs = ctypes.cast(keep[-1], ctypes.c_void_p)
-            e.iss_len, e.sub_len, e.jti_len = (len(x) for x in strs)
-            e.naud = len(auds)
-            for k, a in enumerate(auds[:MAX_AUD]):
-                e.aud_len[k] = len(a)
-            e.now_sec, e.now_nsec = int(expect["now_sec"]), int(expect["now_nsec"])
-            e.skew_ns = int(expect["skew_ns"])
-            e.exp_leeway_s, e.nbf_leeway_s = int(expect["exp_leeway_s"]), int(expect["nbf_leeway_s"])
-        paths = [[bytes(c) for c in path] for path in paths]
-        ps = JgPaths()
-        ps.n = len(paths)
-        nblob = b""
-        for k, path in enumerate(paths[:MAX_PATHS]):
-            ps.ncomp[k] = len(path)
-            for d, c in enumerate(path[:PATH_MAX_COMP]):        # past what the struct holds the path is refused on its count
-                ps.comp_len[k][d] = len(c)
-                nblob += c
-        nkeep = ctypes.create_string_buffer(nblob, max(1, len(nblob)))
-        ps.names = ctypes.cast(nkeep, ctypes.c_void_p)
-        out = ctypes.create_string_buffer(b"\xee" * max(1, n), max(1, n))
-        vals = (JgClaims * max(1, n))()
-        ctypes.memset(vals, 0xee, ctypes.sizeof(vals))
-        sels = (JgSelected * max(1, n))()
-        ctypes.memset(sels, 0xee, ctypes.sizeof(sels))
-        buf = bytes(arena_bytes) or b"\0"
-        rc = lib().jg_claims_paths(self.h, buf, len(arena_bytes), cj, n, es,
-                                   len(expects) if nexpect is None else nexpect,
-                                   None if "paths" in null else ctypes.byref(ps), out,
-                                   None if "vals" in null else ctypes.cast(vals, ctypes.c_void_p),
-                                   None if "sels" in null else ctypes.cast(sels, ctypes.c_void_p))
-        if rc != 0:
-            raise JgError(f"jg_claims_paths rc={rc}: {self.error()}")
-        return (out.raw[:n], (JgClaims * n).from_buffer_copy(bytes(vals)[:64 * n]),
-                (JgSelected * n).from_buffer_copy(bytes(sels)[:80 * n]))
+        es, _keep = _jg_expects(expects)
+        ps, _nkeep = _jg_paths(paths)
+        out, vals, sels = _poisoned(ctypes.c_char, n), _poisoned(JgClaims, n), _poisoned(JgSelected, n)
+        self._claims_call("jg_claims_paths", arena_bytes, _cjobs(jobs), n, es,
+                          len(expects) if nexpect is None else nexpect,
+                          None if "paths" in null else ctypes.byref(ps), out,
+                          None if "vals" in null else ctypes.cast(vals, ctypes.c_void_p),
+                          None if "sels" in null else ctypes.cast(sels, ctypes.c_void_p))
+        return out.raw[:n], _records(JgClaims, vals, n), _records(JgSelected, sels, n)
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

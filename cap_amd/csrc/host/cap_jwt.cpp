@@ -2730,104 +2730,82 @@ void Validator::SelectColsEach(const std::vector<std::string_view>& tokens, cons
 }
 
 // ====================================================================== oidc hash claims
-void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, uint8_t* digests) {
-  std::shared_lock<std::shared_mutex> life(life_);
+template <class F>
+void Engine::abi_call(const char* name, bool present, bool inside_verify, F&& call) {
+  const std::string entry = std::string("capjwt: ") + name;
+  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
+  if (!inside_verify) life.lock();
   if (!ctx_) fail_device("capjwt: device lost: " + lost_);
-  const int rc = jg_hash_batch(ctx_, arena, arena_len, (const jg_hjob*)jobs, njobs, digests);
-  if (rc == -1) throw std::logic_error(std::string("capjwt: jg_hash_batch rejected the host's jobs: ") + jg_last_error(ctx_));
-  if (rc != 0) fail_device(std::string("capjwt: jg_hash_batch: ") + jg_last_error(ctx_));
+  if (!present) fail_device(entry + ": not provided by the loaded verifier library");
+  const int rc = call();
+  if (rc == -1) throw std::logic_error(entry + " rejected the host's jobs: " + jg_last_error(ctx_));
+  if (rc != 0) fail_device(entry + ": " + jg_last_error(ctx_));
 }
 
-// jg_claims_scan is the one ABI entry the host layer binds weakly: an ABI
-// provider without it (the stub ABI the CPU unit tests link, an older
-// libcapjwt.so) still links, and a CheckBatch against it reports the scan as
-// unavailable, as any other device failure.
-extern "C" __attribute__((weak)) int jg_claims_scan(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
-                                                    const jg_expect*, uint8_t*);
+void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, uint8_t* digests) {
+  abi_call("jg_hash_batch", true, false,
+           [&] { return jg_hash_batch(ctx_, arena, arena_len, (const jg_hjob*)jobs, njobs, digests); });
+}
+
+// The claims entries are the ones the host layer binds weakly: an ABI provider
+// without them (the stub ABI the CPU unit tests link, an older libcapjwt.so)
+// still links, and a CheckBatch against it reports the scan as unavailable, as
+// any other device failure.  jg_claims_scan (CheckBatch), jg_claims_extract
+// (RegisteredBatch), jg_claims_select (SelectBatch), jg_claims_each (the *Each
+// entries: the three scans with a profile per job) and jg_claims_paths (the
+// Select entries by path).
+extern "C" {
+__attribute__((weak)) int jg_claims_scan(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                         uint8_t*);
+__attribute__((weak)) int jg_claims_extract(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                            uint8_t*, jg_claims*);
+__attribute__((weak)) int jg_claims_select(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                           const jg_select*, uint8_t*, jg_claims*, jg_selected*);
+__attribute__((weak)) int jg_claims_each(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                         uint32_t, const jg_select*, uint8_t*, jg_claims*, jg_selected*);
+__attribute__((weak)) int jg_claims_paths(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                          uint32_t, const jg_paths*, uint8_t*, jg_claims*, jg_selected*);
+}
 
 void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
                          uint8_t* codes, bool inside_verify) {
-  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
-  if (!inside_verify) life.lock();
-  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
-  if (!jg_claims_scan) fail_device("capjwt: jg_claims_scan: not provided by the loaded verifier library");
-  const int rc = jg_claims_scan(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect, codes);
-  if (rc == -1)
-    throw std::logic_error(std::string("capjwt: jg_claims_scan rejected the host's jobs: ") + jg_last_error(ctx_));
-  if (rc != 0) fail_device(std::string("capjwt: jg_claims_scan: ") + jg_last_error(ctx_));
+  abi_call("jg_claims_scan", jg_claims_scan != nullptr, inside_verify, [&] {
+    return jg_claims_scan(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect, codes);
+  });
 }
-
-// ... and so is jg_claims_extract (RegisteredBatch), for the same providers
-extern "C" __attribute__((weak)) int jg_claims_extract(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
-                                                       const jg_expect*, uint8_t*, jg_claims*);
 
 void Engine::claims_extract(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
                             uint8_t* codes, void* vals, bool inside_verify) {
-  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
-  if (!inside_verify) life.lock();
-  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
-  if (!jg_claims_extract) fail_device("capjwt: jg_claims_extract: not provided by the loaded verifier library");
-  const int rc = jg_claims_extract(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect, codes,
-                                   (jg_claims*)vals);
-  if (rc == -1)
-    throw std::logic_error(std::string("capjwt: jg_claims_extract rejected the host's jobs: ") + jg_last_error(ctx_));
-  if (rc != 0) fail_device(std::string("capjwt: jg_claims_extract: ") + jg_last_error(ctx_));
+  abi_call("jg_claims_extract", jg_claims_extract != nullptr, inside_verify, [&] {
+    return jg_claims_extract(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect, codes,
+                             (jg_claims*)vals);
+  });
 }
-
-// ... and jg_claims_select (SelectBatch)
-extern "C" __attribute__((weak)) int jg_claims_select(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
-                                                      const jg_expect*, const jg_select*, uint8_t*, jg_claims*,
-                                                      jg_selected*);
 
 void Engine::claims_select(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
                            const void* select, uint8_t* codes, void* vals, void* sels, bool inside_verify) {
-  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
-  if (!inside_verify) life.lock();
-  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
-  if (!jg_claims_select) fail_device("capjwt: jg_claims_select: not provided by the loaded verifier library");
-  const int rc = jg_claims_select(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect,
-                                  (const jg_select*)select, codes, (jg_claims*)vals, (jg_selected*)sels);
-  if (rc == -1)
-    throw std::logic_error(std::string("capjwt: jg_claims_select rejected the host's jobs: ") + jg_last_error(ctx_));
-  if (rc != 0) fail_device(std::string("capjwt: jg_claims_select: ") + jg_last_error(ctx_));
+  abi_call("jg_claims_select", jg_claims_select != nullptr, inside_verify, [&] {
+    return jg_claims_select(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expect,
+                            (const jg_select*)select, codes, (jg_claims*)vals, (jg_selected*)sels);
+  });
 }
-
-// ... and jg_claims_each (the *Each entries): the three scans with a profile per job
-extern "C" __attribute__((weak)) int jg_claims_each(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
-                                                    const jg_expect*, uint32_t, const jg_select*, uint8_t*, jg_claims*,
-                                                    jg_selected*);
 
 void Engine::claims_each(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                          uint32_t nexpect, const void* select, uint8_t* codes, void* vals, void* sels,
                          bool inside_verify) {
-  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
-  if (!inside_verify) life.lock();
-  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
-  if (!jg_claims_each) fail_device("capjwt: jg_claims_each: not provided by the loaded verifier library");
-  const int rc = jg_claims_each(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
-                                (const jg_select*)select, codes, (jg_claims*)vals, (jg_selected*)sels);
-  if (rc == -1)
-    throw std::logic_error(std::string("capjwt: jg_claims_each rejected the host's jobs: ") + jg_last_error(ctx_));
-  if (rc != 0) fail_device(std::string("capjwt: jg_claims_each: ") + jg_last_error(ctx_));
+  abi_call("jg_claims_each", jg_claims_each != nullptr, inside_verify, [&] {
+    return jg_claims_each(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                          (const jg_select*)select, codes, (jg_claims*)vals, (jg_selected*)sels);
+  });
 }
-
-// ... and jg_claims_paths (the Select entries by path)
-extern "C" __attribute__((weak)) int jg_claims_paths(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t,
-                                                     const jg_expect*, uint32_t, const jg_paths*, uint8_t*, jg_claims*,
-                                                     jg_selected*);
 
 void Engine::claims_paths(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                           uint32_t nexpect, const void* paths, uint8_t* codes, void* vals, void* sels,
                           bool inside_verify) {
-  std::shared_lock<std::shared_mutex> life(life_, std::defer_lock);
-  if (!inside_verify) life.lock();
-  if (!ctx_) fail_device("capjwt: device lost: " + lost_);
-  if (!jg_claims_paths) fail_device("capjwt: jg_claims_paths: not provided by the loaded verifier library");
-  const int rc = jg_claims_paths(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects,
-                                 nexpect, (const jg_paths*)paths, codes, (jg_claims*)vals, (jg_selected*)sels);
-  if (rc == -1)
-    throw std::logic_error(std::string("capjwt: jg_claims_paths rejected the host's jobs: ") + jg_last_error(ctx_));
-  if (rc != 0) fail_device(std::string("capjwt: jg_claims_paths: ") + jg_last_error(ctx_));
+  abi_call("jg_claims_paths", jg_claims_paths != nullptr, inside_verify, [&] {
+    return jg_claims_paths(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                           (const jg_paths*)paths, codes, (jg_claims*)vals, (jg_selected*)sels);
+  });
 }
 
 namespace {

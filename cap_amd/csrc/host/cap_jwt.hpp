@@ -243,6 +243,12 @@ class Engine {
   int threads() const { return threads_; }
  private:
   void fail_device(const std::string& what);          // count the error; throws DeviceError
+  // One call of the ABI entry `name` on ctx_ (call(): its return code), under
+  // the lifetime lock unless inside_verify.  -1 is a logic_error, a lost
+  // context, an entry the library does not provide (!present) or any other
+  // code a DeviceError.
+  template <class F>
+  void abi_call(const char* name, bool present, bool inside_verify, F&& call);
   std::vector<int> devices_;
   jg_ctx* ctx_ = nullptr;
   std::shared_mutex life_;        // shared: calls on ctx_; unique: recover (ctx_ replaced)

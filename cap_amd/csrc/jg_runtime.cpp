@@ -3466,23 +3466,59 @@ int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
   }
 }
 
-int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
-                   const jg_cjob* jobs, size_t njobs, const jg_expect* expect, uint8_t* code_out) {
-  if (!ctx || !expect || (njobs > 0 && (!jobs || !code_out)) || (arena_len > 0 && !arena)) return -1;
-  if (njobs == 0) return 0;
+namespace {
+
+// One scan of the claims: what the five jg_claims_* entries hand to claims_run.
+// The resolved sides are host objects that `resolve` fills and points these at;
+// each is uploaded into the kept device buffer of its kind, and the kernel is
+// picked from which of them, and which outputs, are there (launch_claims).
+struct ClaimsCall {
+  const uint8_t* arena;
+  size_t arena_len;
+  const jg_cjob* jobs;
+  size_t njobs;
+  uint8_t* code_out;
+  jg_claims* vals_out;                          // NULL: not asked for
+  jg_selected* sel_out;
+  const jgclaims::Expect* expect = nullptr;     // one of these two: every job's flags are 0,
+  const jgclaims::Profiles* table = nullptr;    // or name one of the table's profiles
+  const jgclaims::Select* select = nullptr;     // at most one of these two, with sel_out
+  const jgclaims::Paths* paths = nullptr;
+};
+
+const char kRefuseExpect[] = "more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9";
+const char kRefuseProfiles[] =
+    "no profile or more than 64, strings over 8192 bytes in all, or a profile with more "
+    "than 16 audiences, expected strings over 4096 bytes or now_nsec >= 1e9";
+const char kRefuseSelect[] =
+    "more than 8 names, a name that is empty, over 64 bytes or not printable ASCII "
+    "without quote and backslash, or two equal names";
+const char kRefusePaths[] =
+    "more than 8 paths, a path of no or more than 4 components, a component that is "
+    "empty, over 64 bytes or not printable ASCII without quote and backslash, or two equal paths";
+
+// The one path of a scan, after the entry's own NULL-argument test.  `resolve`
+// is the entry's resolve step: it fills the call's resolved sides and returns
+// NULL, or the sentence that says why it refuses.  One stream and one set of
+// buffers (kept between calls) per context, under a lock of their own, on the
+// first device.
+int claims_run(jg_ctx* ctx, const std::string& entry, ClaimsCall& c, const std::function<const char*()>& resolve) {
+  if (c.njobs == 0) return 0;
   if (ctx->poisoned.load()) {
     ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
     return -2;
   }
-  auto E = std::make_unique<jgclaims::Expect>();
-  if (!jgclaims::resolve(*expect, E.get())) {
-    ctx->set_err("jg_claims_scan: more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9");
+  if (const char* why = resolve()) {
+    ctx->set_err(entry + ": " + why);
     return -1;
   }
+  const size_t arena_len = c.arena_len, njobs = c.njobs;
+  const uint32_t nprofiles = c.table ? c.table->n : 1u;
   for (size_t i = 0; i < njobs; ++i) {
-    const jg_cjob& J = jobs[i];
-    if (J.flags != 0 || J.off > arena_len || J.len > arena_len - J.off) {
-      ctx->set_err("jg_claims_scan: job " + std::to_string(i) + " has flags set or a span past the arena");
+    const jg_cjob& J = c.jobs[i];
+    if (J.flags >= nprofiles || J.off > arena_len || J.len > arena_len - J.off) {
+      ctx->set_err(entry + ": job " + std::to_string(i) +
+                   (c.table ? " names no profile or has a span past the arena" : " has flags set or a span past the arena"));
       return -1;
     }
   }
@@ -3491,17 +3527,30 @@ int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     std::lock_guard<std::mutex> g(d->cl_mu);
     HIPCHK(hipSetDevice(d->id));
     const hipStream_t s = d->clstream;
+    const auto upload = [s](Grow& to, const void* from, size_t bytes) {
+      void* p = to.get(bytes);
+      HIPCHK(hipMemcpyAsync(p, from, bytes, hipMemcpyHostToDevice, s));
+      return p;
+    };
     uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
     HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
-    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
-    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
-    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
-    jgclaims::Expect* e = (jgclaims::Expect*)d->cl_expect.get(sizeof(jgclaims::Expect));
-    HIPCHK(hipMemcpyAsync(e, E.get(), sizeof(jgclaims::Expect), hipMemcpyHostToDevice, s));
-    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
-    launch_claims_scan(a, j, (int64_t)njobs, e, o, s);
+    if (arena_len) HIPCHK(hipMemcpyAsync(a, c.arena, arena_len, hipMemcpyHostToDevice, s));
+    ClaimsLaunch L;
+    L.arena = a;
+    L.jobs = (const jg_cjob*)upload(d->cl_jobs, c.jobs, sizeof(jg_cjob) * njobs);
+    L.n = (int64_t)njobs;
+    if (c.table) L.table = (const jgclaims::Profiles*)upload(d->cl_profiles, c.table, sizeof *c.table);
+    else L.expect = (const jgclaims::Expect*)upload(d->cl_expect, c.expect, sizeof *c.expect);
+    if (c.paths) L.paths = (const jgclaims::Paths*)upload(d->cl_paths, c.paths, sizeof *c.paths);
+    else if (c.select) L.select = (const jgclaims::Select*)upload(d->cl_select, c.select, sizeof *c.select);
+    L.code_out = (uint8_t*)d->cl_out.get(njobs);
+    if (c.vals_out) L.vals_out = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
+    if (c.sel_out) L.sel_out = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
+    launch_claims(L, s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c.code_out, L.code_out, njobs, hipMemcpyDeviceToHost, s));
+    if (c.vals_out) HIPCHK(hipMemcpyAsync(c.vals_out, L.vals_out, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
+    if (c.sel_out) HIPCHK(hipMemcpyAsync(c.sel_out, L.sel_out, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   } catch (const std::exception& e) {
@@ -3510,243 +3559,91 @@ int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
   }
 }
 
-// jg_claims_scan with the records: the same checks, stream, lock and kept
-// buffers, one more device buffer (cl_vals) and one more copy back
+}  // namespace
+
+int jg_claims_scan(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                   const jg_cjob* jobs, size_t njobs, const jg_expect* expect, uint8_t* code_out) {
+  if (!ctx || !expect || (njobs > 0 && (!jobs || !code_out)) || (arena_len > 0 && !arena)) return -1;
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, nullptr, nullptr};
+  auto E = std::make_unique<jgclaims::Expect>();
+  return claims_run(ctx, "jg_claims_scan", c, [&]() -> const char* {
+    if (!jgclaims::resolve(*expect, E.get())) return kRefuseExpect;
+    c.expect = E.get();
+    return nullptr;
+  });
+}
+
+// jg_claims_scan with the records: one more copy back
 int jg_claims_extract(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                       const jg_cjob* jobs, size_t njobs, const jg_expect* expect,
                       uint8_t* code_out, jg_claims* vals_out) {
   if (!ctx || !expect || (njobs > 0 && (!jobs || !code_out || !vals_out)) || (arena_len > 0 && !arena)) return -1;
-  if (njobs == 0) return 0;
-  if (ctx->poisoned.load()) {
-    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
-    return -2;
-  }
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, vals_out, nullptr};
   auto E = std::make_unique<jgclaims::Expect>();
-  if (!jgclaims::resolve(*expect, E.get())) {
-    ctx->set_err("jg_claims_extract: more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9");
-    return -1;
-  }
-  for (size_t i = 0; i < njobs; ++i) {
-    const jg_cjob& J = jobs[i];
-    if (J.flags != 0 || J.off > arena_len || J.len > arena_len - J.off) {
-      ctx->set_err("jg_claims_extract: job " + std::to_string(i) + " has flags set or a span past the arena");
-      return -1;
-    }
-  }
-  try {
-    Device* d = ctx->devs[0].get();
-    std::lock_guard<std::mutex> g(d->cl_mu);
-    HIPCHK(hipSetDevice(d->id));
-    const hipStream_t s = d->clstream;
-    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
-    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
-    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
-    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
-    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
-    jgclaims::Expect* e = (jgclaims::Expect*)d->cl_expect.get(sizeof(jgclaims::Expect));
-    HIPCHK(hipMemcpyAsync(e, E.get(), sizeof(jgclaims::Expect), hipMemcpyHostToDevice, s));
-    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
-    jg_claims* v = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
-    launch_claims_extract(a, j, (int64_t)njobs, e, o, v, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-  } catch (const std::exception& e) {
-    ctx->set_err(e.what());
-    return -2;
-  }
+  return claims_run(ctx, "jg_claims_extract", c, [&]() -> const char* {
+    if (!jgclaims::resolve(*expect, E.get())) return kRefuseExpect;
+    c.expect = E.get();
+    return nullptr;
+  });
 }
 
-// jg_claims_extract with the caller's names: one more kept device buffer
-// (cl_sel), one small upload (the resolved names) and one more copy back
+// jg_claims_extract with the caller's names: one small upload (the resolved
+// names) and one more copy back
 int jg_claims_select(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                      const jg_cjob* jobs, size_t njobs, const jg_expect* expect, const jg_select* select,
                      uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out) {
   if (!ctx || !expect || (njobs > 0 && (!jobs || !code_out || !vals_out || !sel_out || !select)) ||
       (arena_len > 0 && !arena))
     return -1;
-  if (njobs == 0) return 0;
-  if (ctx->poisoned.load()) {
-    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
-    return -2;
-  }
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, vals_out, sel_out};
   auto E = std::make_unique<jgclaims::Expect>();
-  if (!jgclaims::resolve(*expect, E.get())) {
-    ctx->set_err("jg_claims_select: more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9");
-    return -1;
-  }
   auto S = std::make_unique<jgclaims::Select>();
-  if (!jgclaims::resolve_select(*select, S.get())) {
-    ctx->set_err("jg_claims_select: more than 8 names, a name that is empty, over 64 bytes or not printable ASCII "
-                 "without quote and backslash, or two equal names");
-    return -1;
-  }
-  for (size_t i = 0; i < njobs; ++i) {
-    const jg_cjob& J = jobs[i];
-    if (J.flags != 0 || J.off > arena_len || J.len > arena_len - J.off) {
-      ctx->set_err("jg_claims_select: job " + std::to_string(i) + " has flags set or a span past the arena");
-      return -1;
-    }
-  }
-  try {
-    Device* d = ctx->devs[0].get();
-    std::lock_guard<std::mutex> g(d->cl_mu);
-    HIPCHK(hipSetDevice(d->id));
-    const hipStream_t s = d->clstream;
-    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
-    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
-    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
-    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
-    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
-    jgclaims::Expect* e = (jgclaims::Expect*)d->cl_expect.get(sizeof(jgclaims::Expect));
-    HIPCHK(hipMemcpyAsync(e, E.get(), sizeof(jgclaims::Expect), hipMemcpyHostToDevice, s));
-    jgclaims::Select* sl = (jgclaims::Select*)d->cl_select.get(sizeof(jgclaims::Select));
-    HIPCHK(hipMemcpyAsync(sl, S.get(), sizeof(jgclaims::Select), hipMemcpyHostToDevice, s));
-    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
-    jg_claims* v = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
-    jg_selected* q = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
-    launch_claims_select(a, j, (int64_t)njobs, e, sl, o, v, q, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-  } catch (const std::exception& e) {
-    ctx->set_err(e.what());
-    return -2;
-  }
+  return claims_run(ctx, "jg_claims_select", c, [&]() -> const char* {
+    if (!jgclaims::resolve(*expect, E.get())) return kRefuseExpect;
+    if (!jgclaims::resolve_select(*select, S.get())) return kRefuseSelect;
+    c.expect = E.get();
+    c.select = S.get();
+    return nullptr;
+  });
 }
 
-// The three scans with a profile per job: the same checks, stream, lock and kept
-// buffers, one more device buffer (cl_profiles) for the resolved table, which is
-// uploaded whole
+// The three scans with a profile per job: the resolved table in the place of
+// the one Expected, uploaded whole
 int jg_claims_each(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                    const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
                    const jg_select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out) {
   if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out)) || (sel_out && (!select || !vals_out)) ||
       (arena_len > 0 && !arena))
     return -1;
-  if (njobs == 0) return 0;
-  if (ctx->poisoned.load()) {
-    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
-    return -2;
-  }
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, vals_out, sel_out};
   auto T = std::make_unique<jgclaims::Profiles>();
-  if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) {
-    ctx->set_err("jg_claims_each: no profile or more than 64, strings over 8192 bytes in all, or a profile with more "
-                 "than 16 audiences, expected strings over 4096 bytes or now_nsec >= 1e9");
-    return -1;
-  }
   auto S = std::make_unique<jgclaims::Select>();
-  if (sel_out && !jgclaims::resolve_select(*select, S.get())) {
-    ctx->set_err("jg_claims_each: more than 8 names, a name that is empty, over 64 bytes or not printable ASCII "
-                 "without quote and backslash, or two equal names");
-    return -1;
-  }
-  for (size_t i = 0; i < njobs; ++i) {
-    const jg_cjob& J = jobs[i];
-    if (J.flags >= nexpect || J.off > arena_len || J.len > arena_len - J.off) {
-      ctx->set_err("jg_claims_each: job " + std::to_string(i) + " names no profile or has a span past the arena");
-      return -1;
-    }
-  }
-  try {
-    Device* d = ctx->devs[0].get();
-    std::lock_guard<std::mutex> g(d->cl_mu);
-    HIPCHK(hipSetDevice(d->id));
-    const hipStream_t s = d->clstream;
-    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
-    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
-    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
-    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
-    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
-    jgclaims::Profiles* t = (jgclaims::Profiles*)d->cl_profiles.get(sizeof(jgclaims::Profiles));
-    HIPCHK(hipMemcpyAsync(t, T.get(), sizeof(jgclaims::Profiles), hipMemcpyHostToDevice, s));
-    jgclaims::Select* sl = nullptr;
-    if (sel_out) {
-      sl = (jgclaims::Select*)d->cl_select.get(sizeof(jgclaims::Select));
-      HIPCHK(hipMemcpyAsync(sl, S.get(), sizeof(jgclaims::Select), hipMemcpyHostToDevice, s));
-    }
-    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
-    jg_claims* v = vals_out ? (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs) : nullptr;
-    jg_selected* q = sel_out ? (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs) : nullptr;
-    launch_claims_each(a, j, (int64_t)njobs, t, sl, o, v, q, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
-    if (v) HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
-    if (q) HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-  } catch (const std::exception& e) {
-    ctx->set_err(e.what());
-    return -2;
-  }
+  return claims_run(ctx, "jg_claims_each", c, [&]() -> const char* {
+    if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) return kRefuseProfiles;
+    if (sel_out && !jgclaims::resolve_select(*select, S.get())) return kRefuseSelect;
+    c.table = T.get();
+    c.select = sel_out ? S.get() : nullptr;
+    return nullptr;
+  });
 }
 
-// jg_claims_each's selecting form with paths in the place of names: the same
-// checks, stream, lock and kept buffers, one more device buffer (cl_paths) for
-// the resolved paths, which is uploaded whole
+// jg_claims_each's selecting form with paths in the place of names
 int jg_claims_paths(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                     const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
                     const jg_paths* paths, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out) {
   if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out || !paths || !vals_out || !sel_out)) ||
       (arena_len > 0 && !arena))
     return -1;
-  if (njobs == 0) return 0;
-  if (ctx->poisoned.load()) {
-    ctx->set_err("context unusable after an injected device failure (jg_debug_fail_verify): recreate it");
-    return -2;
-  }
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, vals_out, sel_out};
   auto T = std::make_unique<jgclaims::Profiles>();
-  if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) {
-    ctx->set_err("jg_claims_paths: no profile or more than 64, strings over 8192 bytes in all, or a profile with more "
-                 "than 16 audiences, expected strings over 4096 bytes or now_nsec >= 1e9");
-    return -1;
-  }
   auto P = std::make_unique<jgclaims::Paths>();
-  if (!jgclaims::resolve_paths(*paths, P.get())) {
-    ctx->set_err("jg_claims_paths: more than 8 paths, a path of no or more than 4 components, a component that is "
-                 "empty, over 64 bytes or not printable ASCII without quote and backslash, or two equal paths");
-    return -1;
-  }
-  for (size_t i = 0; i < njobs; ++i) {
-    const jg_cjob& J = jobs[i];
-    if (J.flags >= nexpect || J.off > arena_len || J.len > arena_len - J.off) {
-      ctx->set_err("jg_claims_paths: job " + std::to_string(i) + " names no profile or has a span past the arena");
-      return -1;
-    }
-  }
-  try {
-    Device* d = ctx->devs[0].get();
-    std::lock_guard<std::mutex> g(d->cl_mu);
-    HIPCHK(hipSetDevice(d->id));
-    const hipStream_t s = d->clstream;
-    uint8_t* a = (uint8_t*)d->cl_arena.get(arena_len + ARENA_SLACK);
-    HIPCHK(hipMemsetAsync(a + arena_len, 0, ARENA_SLACK, s));
-    if (arena_len) HIPCHK(hipMemcpyAsync(a, arena, arena_len, hipMemcpyHostToDevice, s));
-    jg_cjob* j = (jg_cjob*)d->cl_jobs.get(sizeof(jg_cjob) * njobs);
-    HIPCHK(hipMemcpyAsync(j, jobs, sizeof(jg_cjob) * njobs, hipMemcpyHostToDevice, s));
-    jgclaims::Profiles* t = (jgclaims::Profiles*)d->cl_profiles.get(sizeof(jgclaims::Profiles));
-    HIPCHK(hipMemcpyAsync(t, T.get(), sizeof(jgclaims::Profiles), hipMemcpyHostToDevice, s));
-    jgclaims::Paths* pp = (jgclaims::Paths*)d->cl_paths.get(sizeof(jgclaims::Paths));
-    HIPCHK(hipMemcpyAsync(pp, P.get(), sizeof(jgclaims::Paths), hipMemcpyHostToDevice, s));
-    uint8_t* o = (uint8_t*)d->cl_out.get(njobs);
-    jg_claims* v = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
-    jg_selected* q = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
-    launch_claims_paths(a, j, (int64_t)njobs, t, pp, o, v, q, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(code_out, o, njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(vals_out, v, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(sel_out, q, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-  } catch (const std::exception& e) {
-    ctx->set_err(e.what());
-    return -2;
-  }
+  return claims_run(ctx, "jg_claims_paths", c, [&]() -> const char* {
+    if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) return kRefuseProfiles;
+    if (!jgclaims::resolve_paths(*paths, P.get())) return kRefusePaths;
+    c.table = T.get();
+    c.paths = P.get();
+    return nullptr;
+  });
 }
 
 const char* jg_last_error(jg_ctx* ctx) {

@@ -34,17 +34,65 @@ struct WordSrc {
 
 constexpr int kBlock = 256;
 
-__global__ void __launch_bounds__(kBlock) k_claims_scan(const uint8_t* __restrict__ arena,
-                                                        const jg_cjob* __restrict__ jobs, int64_t n,
-                                                        const Expect* __restrict__ expect,
-                                                        uint8_t* __restrict__ code_out) {
-  __shared__ Expect E;
-  {
-    static_assert(sizeof(Expect) % 4 == 0, "Expect is copied by words");
-    const uint32_t* src = (const uint32_t*)expect;
-    uint32_t* dst = (uint32_t*)&E;
-    for (uint32_t k = threadIdx.x; k < sizeof(Expect) / 4; k += kBlock) dst[k] = src[k];
+// the block copies `words` 32-bit words of *src, from word `first` on, to its LDS object *dst
+template <class T>
+__device__ __forceinline__ void copy_words(T* dst, const T* __restrict__ src, uint32_t first, uint32_t words) {
+  static_assert(sizeof(T) % 4 == 0, "copied to LDS by words");
+  for (uint32_t k = threadIdx.x; k < words; k += kBlock) ((uint32_t*)dst)[first + k] = ((const uint32_t*)src)[first + k];
+}
+
+// the records go out as 16-byte stores: four for a jg_claims, five for a jg_selected
+static_assert(sizeof(jg_claims) == 64, "the record is four 16-byte stores");
+__device__ __forceinline__ void store_claims(jg_claims* out, const jg_claims& v) {
+  uint4* o = (uint4*)out;
+  o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
+  o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
+  o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
+  o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
+}
+static_assert(sizeof(jg_selected) == 80, "the record is five 16-byte stores");
+__device__ __forceinline__ void store_selected(jg_selected* out, const jg_selected& q) {
+  uint4* t = (uint4*)out;
+  t[0] = make_uint4(q.off[0], q.off[1], q.off[2], q.off[3]);
+  t[1] = make_uint4(q.off[4], q.off[5], q.off[6], q.off[7]);
+  t[2] = make_uint4(q.len[0], q.len[1], q.len[2], q.len[3]);
+  t[3] = make_uint4(q.len[4], q.len[5], q.len[6], q.len[7]);
+  t[4] = make_uint4(q.type[0] | (uint32_t)q.type[1] << 8 | (uint32_t)q.type[2] << 16 | (uint32_t)q.type[3] << 24,
+                    q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
+}
+
+// The body of all seven kernels.  M is the scan's mode.  X is the block's LDS
+// copy of the expected side, XS its type:
+//   Expect    one for the call, copied whole;
+//   Profiles  the call's table (jg_claims_each), copied only as far as it is in
+//             use -- the n headers (they follow the two counts) and the pool's
+//             used bytes, not all 16 KiB.  Lane i scans against header
+//             jobs[i].flags; the lanes of a wave may hold different profiles,
+//             which only makes the base of the LDS reads per-lane (their
+//             addresses depend on the lane's position in its value already).
+// S is the LDS copy of what a selecting mode selects by, SL its type: Select's
+// names or, for kPath, Paths.  The records stay in registers (fields and
+// constant indices only) until they are stored.
+template <int M, class XS, class SL>
+__device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restrict__ arena,
+                                            const jg_cjob* __restrict__ jobs, int64_t n, const XS* __restrict__ expect,
+                                            const SL* __restrict__ select, uint8_t* __restrict__ code_out,
+                                            jg_claims* __restrict__ vals_out, jg_selected* __restrict__ sel_out) {
+  constexpr bool kTable = std::is_same_v<XS, Profiles>;
+  uint32_t np = 0;
+  if constexpr (kTable) {
+    static_assert(offsetof(Profiles, h) == 8 && sizeof(ProfileHeader) % 4 == 0 && offsetof(Profiles, pool) % 4 == 0,
+                  "the table is copied by words");
+    uint32_t used = expect->pool_used;
+    np = expect->n;
+    np = np < (uint32_t)JG_MAX_PROFILES ? np : (uint32_t)JG_MAX_PROFILES;       // the runtime resolved it: never taken
+    used = used < (uint32_t)JG_PROFILE_POOL_BYTES ? used : (uint32_t)JG_PROFILE_POOL_BYTES;
+    copy_words(&X, expect, 0u, (8u + np * (uint32_t)sizeof(ProfileHeader)) / 4u);
+    copy_words(&X, expect, offsetof(Profiles, pool) / 4u, (used + 3u) / 4u);
+  } else {
+    copy_words(&X, expect, 0u, sizeof(Expect) / 4u);
   }
+  if constexpr (M >= kSelect) copy_words(S, select, 0u, sizeof(SL) / 4u);
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -53,44 +101,42 @@ __global__ void __launch_bounds__(kBlock) k_claims_scan(const uint8_t* __restric
   src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
   src.shift8 = 8u * (uint32_t)(J.off & 3);
   src.cur = src.aligned[0];
-  code_out[i] = claims_decide(src, J.len, E);
+  jg_claims v;
+  jg_selected q;
+  if constexpr (kTable) {
+    const ProfileRef E{X, J.flags < np ? J.flags : 0u};                         // likewise: checked before the launch
+    code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q);
+  } else {
+    code_out[i] = scan_segment<M>(src, J.len, X, &v, S, &q);
+  }
+  if constexpr (M >= kExtract) store_claims(vals_out + i, v);
+  if constexpr (M >= kSelect) store_selected(sel_out + i, q);
+}
+
+// code_out[i] = the jg_claim_code of jobs[i]
+__global__ void __launch_bounds__(kBlock) k_claims_scan(const uint8_t* __restrict__ arena,
+                                                        const jg_cjob* __restrict__ jobs, int64_t n,
+                                                        const Expect* __restrict__ expect,
+                                                        uint8_t* __restrict__ code_out) {
+  __shared__ Expect E;
+  claims_body<kVerdict, Expect, Select>(E, nullptr, arena, jobs, n, expect, nullptr, code_out, nullptr, nullptr);
 }
 
 // k_claims_scan that also keeps what it read: vals_out[i] is token i's record of
-// registered claims (jg_claims, 64 bytes), written as four 16-byte stores
+// registered claims (jg_claims, 64 bytes)
 __global__ void __launch_bounds__(kBlock) k_claims_extract(const uint8_t* __restrict__ arena,
                                                            const jg_cjob* __restrict__ jobs, int64_t n,
                                                            const Expect* __restrict__ expect,
                                                            uint8_t* __restrict__ code_out,
                                                            jg_claims* __restrict__ vals_out) {
   __shared__ Expect E;
-  {
-    const uint32_t* src = (const uint32_t*)expect;
-    uint32_t* dst = (uint32_t*)&E;
-    for (uint32_t k = threadIdx.x; k < sizeof(Expect) / 4; k += kBlock) dst[k] = src[k];
-  }
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const jg_cjob J = jobs[i];
-  WordSrc src;
-  src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
-  src.shift8 = 8u * (uint32_t)(J.off & 3);
-  src.cur = src.aligned[0];
-  jg_claims v;                                  // fields only: stays in registers
-  code_out[i] = claims_extract(src, J.len, E, &v);
-  static_assert(sizeof(jg_claims) == 64, "the record is four 16-byte stores");
-  uint4* o = (uint4*)(vals_out + i);
-  o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
-  o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
-  o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
-  o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
+  claims_body<kExtract, Expect, Select>(E, nullptr, arena, jobs, n, expect, nullptr, code_out, vals_out, nullptr);
 }
 
 // k_claims_extract that also latches where the caller's named top-level
-// members lie: sel_out[i] is token i's jg_selected (80 bytes), five 16-byte
-// stores.  The resolved names sit in LDS beside the Expected; a depth-1 key is
-// compared with them byte by byte from there.
+// members lie: sel_out[i] is token i's jg_selected (80 bytes).  The resolved
+// names sit in LDS beside the Expected; a depth-1 key is compared with them byte
+// by byte from there.
 __global__ void __launch_bounds__(kBlock) k_claims_select(const uint8_t* __restrict__ arena,
                                                           const jg_cjob* __restrict__ jobs, int64_t n,
                                                           const Expect* __restrict__ expect,
@@ -100,116 +146,17 @@ __global__ void __launch_bounds__(kBlock) k_claims_select(const uint8_t* __restr
                                                           jg_selected* __restrict__ sel_out) {
   __shared__ Expect E;
   __shared__ Select S;
-  {
-    static_assert(sizeof(Select) % 4 == 0, "Select is copied by words");
-    const uint32_t* src = (const uint32_t*)expect;
-    uint32_t* dst = (uint32_t*)&E;
-    for (uint32_t k = threadIdx.x; k < sizeof(Expect) / 4; k += kBlock) dst[k] = src[k];
-    const uint32_t* ssrc = (const uint32_t*)select;
-    uint32_t* sdst = (uint32_t*)&S;
-    for (uint32_t k = threadIdx.x; k < sizeof(Select) / 4; k += kBlock) sdst[k] = ssrc[k];
-  }
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const jg_cjob J = jobs[i];
-  WordSrc src;
-  src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
-  src.shift8 = 8u * (uint32_t)(J.off & 3);
-  src.cur = src.aligned[0];
-  jg_claims v;                                  // fields and constant indices only: both stay in registers
-  jg_selected q;
-  code_out[i] = claims_select(src, J.len, E, S, &v, &q);
-  uint4* o = (uint4*)(vals_out + i);
-  o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
-  o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
-  o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
-  o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
-  static_assert(sizeof(jg_selected) == 80, "the record is five 16-byte stores");
-  uint4* t = (uint4*)(sel_out + i);
-  t[0] = make_uint4(q.off[0], q.off[1], q.off[2], q.off[3]);
-  t[1] = make_uint4(q.off[4], q.off[5], q.off[6], q.off[7]);
-  t[2] = make_uint4(q.len[0], q.len[1], q.len[2], q.len[3]);
-  t[3] = make_uint4(q.len[4], q.len[5], q.len[6], q.len[7]);
-  t[4] = make_uint4(q.type[0] | (uint32_t)q.type[1] << 8 | (uint32_t)q.type[2] << 16 | (uint32_t)q.type[3] << 24,
-                    q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
+  claims_body<kSelect, Expect, Select>(E, &S, arena, jobs, n, expect, select, code_out, vals_out, sel_out);
 }
 
 // The three kernels above with a profile per lane (jg_claims_each): the block
-// holds the call's Profiles table in LDS instead of one Expect, copied by words
-// and only as far as it is in use -- the n headers (they follow the two counts)
-// and the pool's used bytes, not all 16 KiB.  Lane i scans against header
-// jobs[i].flags; the lanes of a wave may hold different profiles, which only
-// makes the base of the LDS reads per-lane (their addresses depend on the lane's
-// position in its value already).  M is the scan's mode; the records are
-// written as above.  SL is what a selecting mode selects by: Select's names or,
-// for kPath, Paths.
-template <int M, class SL>
-__device__ __forceinline__ void claims_each_body(Profiles& T, SL* S, const uint8_t* __restrict__ arena,
-                                                 const jg_cjob* __restrict__ jobs, int64_t n,
-                                                 const Profiles* __restrict__ table,
-                                                 const SL* __restrict__ select, uint8_t* __restrict__ code_out,
-                                                 jg_claims* __restrict__ vals_out, jg_selected* __restrict__ sel_out) {
-  static_assert(offsetof(Profiles, h) == 8 && sizeof(ProfileHeader) % 4 == 0 && offsetof(Profiles, pool) % 4 == 0,
-                "the table is copied by words");
-  uint32_t np = table->n, used = table->pool_used;
-  np = np < (uint32_t)JG_MAX_PROFILES ? np : (uint32_t)JG_MAX_PROFILES;       // the runtime resolved it: never taken
-  used = used < (uint32_t)JG_PROFILE_POOL_BYTES ? used : (uint32_t)JG_PROFILE_POOL_BYTES;
-  {
-    const uint32_t* src = (const uint32_t*)table;
-    uint32_t* dst = (uint32_t*)&T;
-    const uint32_t hw = (8u + np * (uint32_t)sizeof(ProfileHeader)) / 4u;
-    for (uint32_t k = threadIdx.x; k < hw; k += kBlock) dst[k] = src[k];
-    constexpr uint32_t pw0 = offsetof(Profiles, pool) / 4u;
-    const uint32_t pw = (used + 3u) / 4u;
-    for (uint32_t k = threadIdx.x; k < pw; k += kBlock) dst[pw0 + k] = src[pw0 + k];
-    if constexpr (M >= kSelect) {
-      static_assert(sizeof(SL) % 4 == 0, "the names are copied by words");
-      const uint32_t* ssrc = (const uint32_t*)select;
-      uint32_t* sdst = (uint32_t*)S;
-      for (uint32_t k = threadIdx.x; k < sizeof(SL) / 4; k += kBlock) sdst[k] = ssrc[k];
-    }
-  }
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const jg_cjob J = jobs[i];
-  const uint32_t p = J.flags < np ? J.flags : 0u;                             // likewise: checked before the launch
-  WordSrc src;
-  src.aligned = (const uint32_t*)(arena + (J.off & ~(uint64_t)3));
-  src.shift8 = 8u * (uint32_t)(J.off & 3);
-  src.cur = src.aligned[0];
-  if constexpr (M == kVerdict) {
-    code_out[i] = claims_decide_each(src, J.len, T, p);
-  } else {
-    jg_claims v;
-    jg_selected q;
-    if constexpr (M == kPath) code_out[i] = claims_paths_each(src, J.len, T, p, *S, &v, &q);
-    else if constexpr (M == kSelect) code_out[i] = claims_select_each(src, J.len, T, p, *S, &v, &q);
-    else code_out[i] = claims_extract_each(src, J.len, T, p, &v);
-    uint4* o = (uint4*)(vals_out + i);
-    o[0] = make_uint4((uint32_t)v.exp, (uint32_t)((uint64_t)v.exp >> 32), (uint32_t)v.nbf, (uint32_t)((uint64_t)v.nbf >> 32));
-    o[1] = make_uint4((uint32_t)v.iat, (uint32_t)((uint64_t)v.iat >> 32), v.iss_off, v.iss_len);
-    o[2] = make_uint4(v.sub_off, v.sub_len, v.jti_off, v.jti_len);
-    o[3] = make_uint4(v.aud_off, v.aud_len, v.aud_n, v.present);
-    if constexpr (M >= kSelect) {
-      uint4* t = (uint4*)(sel_out + i);
-      t[0] = make_uint4(q.off[0], q.off[1], q.off[2], q.off[3]);
-      t[1] = make_uint4(q.off[4], q.off[5], q.off[6], q.off[7]);
-      t[2] = make_uint4(q.len[0], q.len[1], q.len[2], q.len[3]);
-      t[3] = make_uint4(q.len[4], q.len[5], q.len[6], q.len[7]);
-      t[4] = make_uint4(q.type[0] | (uint32_t)q.type[1] << 8 | (uint32_t)q.type[2] << 16 | (uint32_t)q.type[3] << 24,
-                        q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
-    }
-  }
-}
-
+// holds the call's Profiles table in LDS instead of one Expect.
 __global__ void __launch_bounds__(kBlock) k_claims_scan_each(const uint8_t* __restrict__ arena,
                                                              const jg_cjob* __restrict__ jobs, int64_t n,
                                                              const Profiles* __restrict__ table,
                                                              uint8_t* __restrict__ code_out) {
   __shared__ Profiles T;
-  claims_each_body<kVerdict, Select>(T, nullptr, arena, jobs, n, table, nullptr, code_out, nullptr, nullptr);
+  claims_body<kVerdict, Profiles, Select>(T, nullptr, arena, jobs, n, table, nullptr, code_out, nullptr, nullptr);
 }
 
 __global__ void __launch_bounds__(kBlock) k_claims_extract_each(const uint8_t* __restrict__ arena,
@@ -218,7 +165,7 @@ __global__ void __launch_bounds__(kBlock) k_claims_extract_each(const uint8_t* _
                                                                 uint8_t* __restrict__ code_out,
                                                                 jg_claims* __restrict__ vals_out) {
   __shared__ Profiles T;
-  claims_each_body<kExtract, Select>(T, nullptr, arena, jobs, n, table, nullptr, code_out, vals_out, nullptr);
+  claims_body<kExtract, Profiles, Select>(T, nullptr, arena, jobs, n, table, nullptr, code_out, vals_out, nullptr);
 }
 
 __global__ void __launch_bounds__(kBlock) k_claims_select_each(const uint8_t* __restrict__ arena,
@@ -230,7 +177,7 @@ __global__ void __launch_bounds__(kBlock) k_claims_select_each(const uint8_t* __
                                                                jg_selected* __restrict__ sel_out) {
   __shared__ Profiles T;
   __shared__ Select S;
-  claims_each_body<kSelect, Select>(T, &S, arena, jobs, n, table, select, code_out, vals_out, sel_out);
+  claims_body<kSelect, Profiles, Select>(T, &S, arena, jobs, n, table, select, code_out, vals_out, sel_out);
 }
 
 // k_claims_select_each for members named by path (jg_claims_paths): the resolved
@@ -245,51 +192,22 @@ __global__ void __launch_bounds__(kBlock) k_claims_paths_each(const uint8_t* __r
                                                               jg_selected* __restrict__ sel_out) {
   __shared__ Profiles T;
   __shared__ Paths P;
-  claims_each_body<kPath, Paths>(T, &P, arena, jobs, n, table, paths, code_out, vals_out, sel_out);
+  claims_body<kPath, Profiles, Paths>(T, &P, arena, jobs, n, table, paths, code_out, vals_out, sel_out);
 }
 
 }  // namespace
 
-void launch_claims_each(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Profiles* table,
-                        const Select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
-                        hipStream_t s) {
-  if (n <= 0) return;
-  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-  if (sel_out)
-    hipLaunchKernelGGL(k_claims_select_each, grid, block, 0, s, arena, jobs, n, table, select, code_out, vals_out,
-                       sel_out);
-  else if (vals_out)
-    hipLaunchKernelGGL(k_claims_extract_each, grid, block, 0, s, arena, jobs, n, table, code_out, vals_out);
-  else
-    hipLaunchKernelGGL(k_claims_scan_each, grid, block, 0, s, arena, jobs, n, table, code_out);
-}
-
-void launch_claims_paths(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Profiles* table,
-                         const Paths* paths, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
-                         hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_claims_paths_each, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs,
-                     n, table, paths, code_out, vals_out, sel_out);
-}
-
-void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
-                          const Select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
-                          hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_claims_select, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs, n,
-                     expect, select, code_out, vals_out, sel_out);
-}
-
-void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
-                           uint8_t* code_out, jg_claims* vals_out, hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_claims_extract, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs, n,
-                     expect, code_out, vals_out);
-}
-
-void launch_claims_scan(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const Expect* expect,
-                        uint8_t* code_out, hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_claims_scan, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, arena, jobs, n,
-                     expect, code_out);
+void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
+  if (c.n <= 0) return;
+  const dim3 grid((unsigned)((c.n + kBlock - 1) / kBlock)), block(kBlock);
+  const auto go = [&](auto kernel, auto... rest) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, c.arena, c.jobs, c.n, rest...);
+  };
+  if (c.paths) go(k_claims_paths_each, c.table, c.paths, c.code_out, c.vals_out, c.sel_out);
+  else if (c.table && c.sel_out) go(k_claims_select_each, c.table, c.select, c.code_out, c.vals_out, c.sel_out);
+  else if (c.table && c.vals_out) go(k_claims_extract_each, c.table, c.code_out, c.vals_out);
+  else if (c.table) go(k_claims_scan_each, c.table, c.code_out);
+  else if (c.sel_out) go(k_claims_select, c.expect, c.select, c.code_out, c.vals_out, c.sel_out);
+  else if (c.vals_out) go(k_claims_extract, c.expect, c.code_out, c.vals_out);
+  else go(k_claims_scan, c.expect, c.code_out);
 }

@@ -90,28 +90,42 @@ JG_CL_HD void time_add(int64_t sec, int64_t nsec, int64_t d, int64_t* osec, int3
   *onsec = (int32_t)n2;
 }
 
-// Fills *E from the ABI's jg_expect.  False: more than JG_MAX_AUD audiences,
-// strings over JG_EXPECT_MAX_BYTES in total (or one over 65535), a bad now.
-inline bool resolve(const jg_expect& x, Expect* E) {
+// What resolve() and resolve_profiles() share: one jg_expect into H (an Expect
+// or a ProfileHeader: the same fields) -- the window's edges, the leeways and the
+// 19 lengths and offsets -- with its string bytes copied to dst from *o on, which
+// moves past them.  An empty string's offset is the running one, or 0 with
+// empty_at_zero.  False, before anything is written: more than JG_MAX_AUD
+// audiences, a bad now, strings over JG_EXPECT_MAX_BYTES in total or past `room`.
+template <class H>
+inline bool resolve_one(const jg_expect& x, H* h, uint8_t* dst, uint32_t* o, uint32_t room, bool empty_at_zero) {
   if (x.naud > JG_MAX_AUD || x.now_nsec >= (uint32_t)kNsPerSec) return false;
   uint64_t total = (uint64_t)x.iss_len + x.sub_len + x.jti_len;
   for (uint32_t k = 0; k < x.naud; ++k) total += x.aud_len[k];
-  if (total > JG_EXPECT_MAX_BYTES || (total && !x.strs)) return false;
+  if (total > JG_EXPECT_MAX_BYTES || (total && !x.strs) || *o + total > room) return false;
   int32_t hi_ns;
-  time_add(x.now_sec + kUnixToInternal, x.now_nsec, x.skew_ns, &E->hi_sec, &hi_ns);
-  time_add(x.now_sec + kUnixToInternal, x.now_nsec, -x.skew_ns, &E->lo_sec, &E->lo_ns);
-  E->naud = x.naud;
-  E->exp_leeway_s = x.exp_leeway_s;
-  E->nbf_leeway_s = x.nbf_leeway_s;
-  uint32_t o = 0;
+  time_add(x.now_sec + kUnixToInternal, x.now_nsec, x.skew_ns, &h->hi_sec, &hi_ns);
+  time_add(x.now_sec + kUnixToInternal, x.now_nsec, -x.skew_ns, &h->lo_sec, &h->lo_ns);
+  h->naud = x.naud;
+  h->exp_leeway_s = x.exp_leeway_s;
+  h->nbf_leeway_s = x.nbf_leeway_s;
+  uint32_t so = 0;                                   // within x.strs
   for (int k = 0; k < kStrings; ++k) {
     const uint32_t l = k == 0 ? x.iss_len : k == 1 ? x.sub_len : k == 2 ? x.jti_len
                        : (uint32_t)(k - 3) < x.naud ? x.aud_len[k - 3] : 0u;
-    E->len[k] = (uint16_t)l;
-    E->off[k] = (uint16_t)o;
-    for (uint32_t b = 0; b < l; ++b) E->bytes[o + b] = x.strs[o + b];
-    o += l;
+    h->len[k] = (uint16_t)l;
+    h->off[k] = (uint16_t)(l || !empty_at_zero ? *o : 0u);
+    for (uint32_t b = 0; b < l; ++b) dst[*o + b] = x.strs[so + b];
+    *o += l;
+    so += l;
   }
+  return true;
+}
+
+// Fills *E from the ABI's jg_expect.  False: more than JG_MAX_AUD audiences,
+// strings over JG_EXPECT_MAX_BYTES in total (or one over 65535), a bad now.
+inline bool resolve(const jg_expect& x, Expect* E) {
+  uint32_t o = 0;
+  if (!resolve_one(x, E, E->bytes, &o, JG_EXPECT_MAX_BYTES, false)) return false;
   for (uint32_t b = o; b < JG_EXPECT_MAX_BYTES; ++b) E->bytes[b] = 0;
   return true;
 }
@@ -149,30 +163,9 @@ inline bool resolve_profiles(const jg_expect* x, uint32_t n, Profiles* T) {
   if (!x || n == 0 || n > JG_MAX_PROFILES) return false;
   uint32_t o = 0;
   for (uint32_t p = 0; p < n; ++p) {
-    const jg_expect& X = x[p];
-    if (X.naud > JG_MAX_AUD || X.now_nsec >= (uint32_t)kNsPerSec) return false;
-    uint64_t total = (uint64_t)X.iss_len + X.sub_len + X.jti_len;
-    for (uint32_t k = 0; k < X.naud; ++k) total += X.aud_len[k];
-    if (total > JG_EXPECT_MAX_BYTES || (total && !X.strs)) return false;
-    if (o + total > JG_PROFILE_POOL_BYTES) return false;
-    ProfileHeader& H = T->h[p];
-    int32_t hi_ns;
-    time_add(X.now_sec + kUnixToInternal, X.now_nsec, X.skew_ns, &H.hi_sec, &hi_ns);
-    time_add(X.now_sec + kUnixToInternal, X.now_nsec, -X.skew_ns, &H.lo_sec, &H.lo_ns);
-    H.naud = X.naud;
-    H.exp_leeway_s = X.exp_leeway_s;
-    H.nbf_leeway_s = X.nbf_leeway_s;
-    H.pad_ = 0;
-    uint32_t so = 0;                                 // within this profile's strs
-    for (int k = 0; k < kStrings; ++k) {
-      const uint32_t l = k == 0 ? X.iss_len : k == 1 ? X.sub_len : k == 2 ? X.jti_len
-                         : (uint32_t)(k - 3) < X.naud ? X.aud_len[k - 3] : 0u;
-      H.len[k] = (uint16_t)l;
-      H.off[k] = (uint16_t)(l ? o : 0u);             // an empty string is never read: keep the offset in 16 bits
-      for (uint32_t b = 0; b < l; ++b) T->pool[o + b] = X.strs[so + b];
-      o += l;
-      so += l;
-    }
+    // an empty string is never read: its offset 0 keeps every offset in 16 bits
+    if (!resolve_one(x[p], &T->h[p], T->pool, &o, JG_PROFILE_POOL_BYTES, true)) return false;
+    T->h[p].pad_ = 0;
   }
   for (uint32_t p = n; p < JG_MAX_PROFILES; ++p) T->h[p] = ProfileHeader{};
   for (uint32_t b = o; b < JG_PROFILE_POOL_BYTES; ++b) T->pool[b] = 0;
@@ -206,22 +199,28 @@ struct Select {
   uint8_t bytes[JG_MAX_SELECT * JG_SELECT_NAME_MAX];
 };
 
+// A claim name as resolve_select() and resolve_paths() take one: 1 to
+// JG_SELECT_NAME_MAX bytes, each in 0x20..0x7e and neither a quote nor a backslash
+inline bool name_byte_ok(uint8_t c) { return c >= 0x20u && c <= 0x7eu && c != '"' && c != '\\'; }
+inline bool copy_name(const uint8_t* src, uint32_t l, uint8_t* dst) {
+  if (!src || l == 0 || l > JG_SELECT_NAME_MAX) return false;
+  for (uint32_t b = 0; b < l; ++b) {
+    if (!name_byte_ok(src[b])) return false;
+    dst[b] = src[b];
+  }
+  return true;
+}
+
 // Fills *S from the ABI's jg_select.  False: more than JG_MAX_SELECT names, a
-// name that is empty or longer than JG_SELECT_NAME_MAX, a name byte outside
-// 0x20..0x7e or equal to " or \, two equal names.
+// name copy_name() refuses, two equal names.
 inline bool resolve_select(const jg_select& x, Select* S) {
   if (x.n > JG_MAX_SELECT) return false;
   uint32_t o = 0;
   for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
     const uint32_t l = k < x.n ? x.name_len[k] : 0u;
-    if (k < x.n && (l == 0 || l > JG_SELECT_NAME_MAX || !x.names)) return false;
+    if (k < x.n && !copy_name(x.names ? x.names + o : nullptr, l, S->bytes + o)) return false;
     S->len[k] = (uint16_t)l;
     S->off[k] = (uint16_t)o;
-    for (uint32_t b = 0; b < l; ++b) {
-      const uint8_t c = x.names[o + b];
-      if (c < 0x20u || c > 0x7eu || c == '"' || c == '\\') return false;
-      S->bytes[o + b] = c;
-    }
     for (uint32_t j = 0; j < k; ++j) {
       if (S->len[j] != l || l == 0) continue;
       uint32_t b = 0;
@@ -250,8 +249,8 @@ static_assert(sizeof(Paths) == 4 + 16 + 8 + 32 + 64 + 2048, "no padding in the p
 static_assert(JG_MAX_PATHS == JG_MAX_SELECT && JG_PATH_MAX_COMP == 4, "a path per jg_selected slot, two bits of matched depth");
 
 // Fills *P from the ABI's jg_paths.  False: more than JG_MAX_PATHS paths, a path
-// of no or more than JG_PATH_MAX_COMP components, a component resolve_select
-// refuses as a name, two equal paths.
+// of no or more than JG_PATH_MAX_COMP components, a component copy_name()
+// refuses, two equal paths.
 inline bool resolve_paths(const jg_paths& x, Paths* P) {
   if (x.n > JG_MAX_PATHS) return false;
   *P = Paths{};
@@ -262,14 +261,9 @@ inline bool resolve_paths(const jg_paths& x, Paths* P) {
     P->ncomp[k] = (uint8_t)nc;
     for (uint32_t d = 0; d < nc; ++d) {
       const uint32_t l = x.comp_len[k][d];
-      if (l == 0 || l > JG_SELECT_NAME_MAX) return false;
+      if (!copy_name(x.names + o, l, P->pool + o)) return false;
       P->len[k][d] = (uint8_t)l;
       P->off[k][d] = (uint16_t)o;
-      for (uint32_t b = 0; b < l; ++b) {
-        const uint8_t c = x.names[o + b];
-        if (c < 0x20u || c > 0x7eu || c == '"' || c == '\\') return false;
-        P->pool[o + b] = c;
-      }
       o += l;
       P->ge[d] |= 1u << (2u * k);
     }
@@ -882,25 +876,24 @@ JG_CL_HD uint8_t claims_paths_each(Src& src, uint32_t len, const Profiles& T, ui
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-// code_out[i] = the jg_claim_code of jobs[i]; `expect` is a device jgclaims::Expect
-void launch_claims_scan(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
-                        uint8_t* code_out, hipStream_t s);
-// ... and vals_out[i] = its registered claims (k_claims_extract)
-void launch_claims_extract(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
-                           uint8_t* code_out, jg_claims* vals_out, hipStream_t s);
-// ... and sel_out[i] = the members `select` (a device jgclaims::Select) names (k_claims_select)
-void launch_claims_select(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Expect* expect,
-                          const jgclaims::Select* select, uint8_t* code_out, jg_claims* vals_out,
-                          jg_selected* sel_out, hipStream_t s);
-// The three scans with a profile per job: `table` is a device jgclaims::Profiles
-// and jobs[i].flags (< table->n) names job i's profile.  sel_out: k_claims_select_each
-// (with `select` and vals_out); else vals_out: k_claims_extract_each; else k_claims_scan_each
-void launch_claims_each(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Profiles* table,
-                        const jgclaims::Select* select, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
-                        hipStream_t s);
-// k_claims_paths_each: launch_claims_each's selecting form with `paths` (a device jgclaims::Paths)
-// in the place of the names
-void launch_claims_paths(const uint8_t* arena, const jg_cjob* jobs, int64_t n, const jgclaims::Profiles* table,
-                         const jgclaims::Paths* paths, uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out,
-                         hipStream_t s);
+// One launch of the scan: code_out[i] = the jg_claim_code of jobs[i].  Every
+// pointer is a device one.  What the struct holds picks the kernel:
+//   expect           one Expected for the call; every job's flags are 0
+//   table            a profile per job: jobs[i].flags (< table->n) names job i's
+//   neither select nor paths: vals_out ? k_claims_extract[_each] : k_claims_scan[_each]
+//   select, sel_out  k_claims_select[_each]: and sel_out[i] = the members `select` names (with vals_out)
+//   paths, sel_out   k_claims_paths_each: `paths` in the place of the names (with table and vals_out)
+struct ClaimsLaunch {
+  const uint8_t* arena = nullptr;
+  const jg_cjob* jobs = nullptr;
+  int64_t n = 0;
+  const jgclaims::Expect* expect = nullptr;
+  const jgclaims::Profiles* table = nullptr;
+  const jgclaims::Select* select = nullptr;
+  const jgclaims::Paths* paths = nullptr;
+  uint8_t* code_out = nullptr;
+  jg_claims* vals_out = nullptr;
+  jg_selected* sel_out = nullptr;
+};
+void launch_claims(const ClaimsLaunch& c, hipStream_t s);
 #endif
