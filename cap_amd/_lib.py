@@ -28,7 +28,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest", "jg_debug_table_read",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
            "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
-           "jg_claims_paths"]
+           "jg_claims_paths", "jg_claims_match"]
 
 
 class JgKey(ctypes.Structure):
@@ -119,6 +119,17 @@ class JgPaths(ctypes.Structure):
                 ("comp_len", (ctypes.c_uint32 * PATH_MAX_COMP) * MAX_PATHS)]
 
 
+MAX_PRED, PRED_VALUE_MAX = 16, 64            # JG_MAX_PRED, JG_PRED_VALUE_MAX
+# jg_pred_op
+PRED_EQUALS, PRED_HAS_WORD, PRED_HAS_ELEMENT, PRED_PRESENT = 1, 2, 3, 4
+
+
+class JgPreds(ctypes.Structure):
+    """jg_preds: the caller's predicates, their values back to back in `values`"""
+    _fields_ = [("values", ctypes.c_void_p), ("n", ctypes.c_uint32), ("path", ctypes.c_uint8 * MAX_PRED),
+                ("op", ctypes.c_uint8 * MAX_PRED), ("value_len", ctypes.c_uint32 * MAX_PRED)]
+
+
 def _cjobs(rows):
     """(off, len, flags) rows -> a JgCJob array (of one unused job for no rows)"""
     rows = list(rows)
@@ -182,6 +193,20 @@ def _jg_paths(paths):
     return ps, keep
 
 
+def _jg_preds(preds):
+    """Predicates, each (path index, op, value bytes) -> (JgPreds, the buffer to keep alive)"""
+    preds = [(int(p), int(op), bytes(v)) for p, op, v in preds]
+    ps = JgPreds()
+    ps.n = len(preds)
+    blob = b""
+    for k, (path, op, value) in enumerate(preds[:MAX_PRED]):   # past what the struct holds the list is refused on its count
+        ps.path[k], ps.op[k], ps.value_len[k] = path, op, len(value)
+        blob += value
+    keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+    ps.values = ctypes.cast(keep, ctypes.c_void_p)
+    return ps, keep
+
+
 def _poisoned(ctype, n):
     """An output array of max(1, n) records, every byte 0xee"""
     buf = (ctype * max(1, n))()
@@ -242,6 +267,8 @@ def lib():
                                      ctypes.c_uint32, ctypes.POINTER(JgSelect), vp, vp, vp]
         L.jg_claims_paths.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
                                       ctypes.c_uint32, ctypes.POINTER(JgPaths), vp, vp, vp]
+        L.jg_claims_match.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                      ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds), vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -533,6 +560,27 @@ class Context:
                           None if "vals" in null else ctypes.cast(vals, ctypes.c_void_p),
                           None if "sels" in null else ctypes.cast(sels, ctypes.c_void_p))
         return out.raw[:n], _records(JgClaims, vals, n), _records(JgSelected, sels, n)
+
+    def claims_match(self, arena_bytes, jobs, expects, paths, preds, nexpect=None, null=()):
+        """jg_claims_match: claims_each's codes and, per job, the mask of the
+        predicates that hold on the members `paths` reach.  `jobs`, `expects` and
+        `paths` as claims_paths takes them; `preds`: a list of (path index, op,
+        value bytes) with op one of PRED_* -> (codes: bytes, masks: list of int).
+        Both outputs are poisoned with 0xee before the call.  `nexpect` overrides
+        the count passed to the ABI and `null` names arguments ("paths", "preds",
+        "codes", "masks") to pass as NULL (both for its argument checks)."""
+        n = len(jobs)
+        es, _keep = _jg_expects(expects)
+        ps, _nkeep = _jg_paths(paths)
+        qs, _vkeep = _jg_preds(preds)
+        out, masks = _poisoned(ctypes.c_char, n), _poisoned(ctypes.c_uint32, n)
+        self._claims_call("jg_claims_match", arena_bytes, _cjobs(jobs), n, es,
+                          len(expects) if nexpect is None else nexpect,
+                          None if "paths" in null else ctypes.byref(ps),
+                          None if "preds" in null else ctypes.byref(qs),
+                          None if "codes" in null else out,
+                          None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
+        return out.raw[:n], list(masks[:n])
 
     def set_chunk(self, jobs):
         if lib().jg_set_chunk(self.h, jobs) != 0:

@@ -1983,8 +1983,34 @@ RegisteredClaims claims_of_record(std::string_view seg, const jg_claims& v) {
 // records, record(...) also receives token i's jg_selected and claims(...) the
 // verified claims map of the host-path token.  M = kPathMode: kSelectMode with
 // the caller's paths (`paths`, nullptr as for `select`) and jg_claims_paths as
-// the scan, with one Expected too (a table of one profile).
-constexpr int kCheckMode = 0, kRegisteredMode = 1, kSelectMode = 2, kPathMode = 3;
+// the scan, with one Expected too (a table of one profile).  M = kMatchMode
+// (MatchBatch): kCheckMode with jg_claims_match as the scan (`match`: its paths
+// and predicates, or not scannable: every token takes the host path) and a mask
+// per token behind the jobs; put(i, ok, err, bits) also receives the mask of an
+// accepted token -- the scan's, or match_requires() on the verified claims map.
+constexpr int kCheckMode = 0, kRegisteredMode = 1, kSelectMode = 2, kPathMode = 3, kMatchMode = 4;
+
+// The requirements of a MatchBatch call as the scan takes them (jg_paths and
+// jg_preds): equal paths share a slot, equal requirements a predicate (bit[k]:
+// the scan's bit for requires[k]).  usable == false: the ABI does not take the
+// list and every token goes the host path.
+struct MatchPlan {
+  const std::vector<Require>& reqs;
+  std::string names, values;
+  jg_paths paths{};
+  jg_preds preds{};
+  std::vector<int> bit;
+  bool usable = true;
+  bool identity = true;                              // bit[k] == k for every k: the scan's mask is the caller's
+  explicit MatchPlan(const std::vector<Require>& reqs);
+  // the caller's mask from the scan's
+  uint32_t spread(uint32_t m) const {
+    if (identity) return m;
+    uint32_t out = 0;
+    for (size_t k = 0; k < bit.size(); ++k) out |= ((m >> bit[k]) & 1u) << k;
+    return out;
+  }
+};
 
 // One Expected as the scan takes it (include/jg.h jg_expect) and the clock its
 // tokens are held to.  scannable == false: one the ABI does not take (more than
@@ -2034,11 +2060,12 @@ void resolve_scan_profile(const Expected& expected, int64_t now, ScanProfile* P)
 template <int M, bool Each, class Put>
 void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const Expected* exps, size_t nexp,
                 const uint32_t* which, CheckStats* stats, Put&& put, const jg_select* select = nullptr,
-                const jg_paths* paths = nullptr) {
-  constexpr bool X = M >= kRegisteredMode;
+                const jg_paths* paths = nullptr, const MatchPlan* match = nullptr) {
+  constexpr bool X = M >= kRegisteredMode && M != kMatchMode;
   // a token that is not accepted carries no claims
   auto reject = [&](size_t c, size_t i, std::string&& err) {
     if constexpr (X) put.reject(c, i, std::move(err));
+    else if constexpr (M == kMatchMode) put(i, false, std::move(err), 0u);
     else put(i, false, std::move(err));
   };
   const size_t n = tokens.size();
@@ -2061,6 +2088,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
       bool fits = prof[p].scannable;
       if constexpr (M == kSelectMode) fits = fits && select != nullptr;
       if constexpr (M == kPathMode) fits = fits && paths != nullptr;
+      if constexpr (M == kMatchMode) fits = fits && match->usable;
       if constexpr (Each)
         fits = fits && exs.size() < JG_MAX_PROFILES && pool + prof[p].strs.size() <= JG_PROFILE_POOL_BYTES;
       if (!fits) continue;
@@ -2077,13 +2105,16 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   // Both arrays live in one pinned block of the engine's pool (DMA at link
   // speed, no page faults in steady state).
   Engine& eng = ks_->engine();
-  const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | selected | codes
-  const size_t sel_bytes = M >= kSelectMode ? n * sizeof(jg_selected) : 0;
-  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + rec_bytes + sel_bytes + 16);
+  const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | selected | masks | codes
+  const size_t sel_bytes = X && M >= kSelectMode ? n * sizeof(jg_selected) : 0;
+  const size_t mask_bytes = M == kMatchMode ? n * sizeof(uint32_t) : 0;
+  Engine::Pinned scanbuf = eng.pinned(n * (sizeof(jg_cjob) + 1) + rec_bytes + sel_bytes + mask_bytes + 16);
   jg_cjob* const jobs = (jg_cjob*)scanbuf.get();
   jg_claims* const recs = (jg_claims*)(scanbuf.get() + n * sizeof(jg_cjob));
   jg_selected* const sels = (jg_selected*)(scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes);
-  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes + sel_bytes;
+  uint32_t* const masks = (uint32_t*)(scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes + sel_bytes);
+  uint8_t* const code = scanbuf.get() + n * sizeof(jg_cjob) + rec_bytes + sel_bytes + mask_bytes;
+  (void)masks;
   std::memset(code, JG_CL_HOST, n);
   bool have_jobs = false;
   bool scan_failed = false;
@@ -2116,7 +2147,10 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     pt.lap("scan-jobs");
     try {
       const jg_expect& ex = exs[0];
-      if constexpr (M == kPathMode)
+      if constexpr (M == kMatchMode)
+        eng.claims_match(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths, &match->preds,
+                         code, masks, true);
+      else if constexpr (M == kPathMode)
         eng.claims_paths(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), paths, code, recs, sels, true);
       else if constexpr (Each)
         eng.claims_each(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(),
@@ -2173,7 +2207,12 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
           else put.claims(c, i, std::move(rc));
         } else {
           Result v = validate_claims(r.claims, t.view(), expected, now);
-          put(i, v.ok, std::move(v.err));
+          if constexpr (M == kMatchMode) {
+            const uint32_t bits = v.ok ? match_requires(r.claims, match->reqs) : 0u;
+            put(i, v.ok, std::move(v.err), bits);
+          } else {
+            put(i, v.ok, std::move(v.err));
+          }
         }
         continue;
       }
@@ -2190,6 +2229,9 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
           put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i], sels[i]);
         else
           put.record(c, i, std::string_view(t.lit + t.si_len - jobs[i].len, jobs[i].len), recs[i]);
+      } else if constexpr (M == kMatchMode) {
+        put(i, code[i] == JG_CL_OK, std::string(claim_code_error(code[i])),
+            code[i] == JG_CL_OK ? match->spread(masks[i]) : 0u);
       } else {
         put(i, code[i] == JG_CL_OK, std::string(claim_code_error(code[i])));
       }
@@ -2747,13 +2789,176 @@ void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size
            [&] { return jg_hash_batch(ctx_, arena, arena_len, (const jg_hjob*)jobs, njobs, digests); });
 }
 
+// ---- MatchBatch: predicates on claims, answered by the scan ----
+namespace {
+// what MatchBatch refuses whatever path decides the tokens
+void check_requires(const std::vector<Require>& reqs) {
+  if (reqs.size() > kMaxRequires) throw std::invalid_argument("capjwt: more than 16 requirements: the mask has no bit for them");
+  for (const Require& r : reqs) {
+    if (r.path.empty()) throw std::invalid_argument("capjwt: a claim path has no component");
+    for (const std::string& comp : r.path)
+      if (comp.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim path holds a NUL byte");
+    if (r.value.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a required value holds a NUL byte");
+    if (r.op < Require::Equals || r.op > Require::Present) throw std::invalid_argument("capjwt: an unknown requirement op");
+  }
+}
+bool scan_byte_ok(unsigned char c) { return c >= 0x20 && c <= 0x7e && c != '"' && c != '\\'; }
+
+MatchPlan::MatchPlan(const std::vector<Require>& reqs) : reqs(reqs), bit(reqs.size(), -1) {
+  check_requires(reqs);
+  std::vector<const ClaimPath*> upaths;
+  std::vector<size_t> upreds;                        // the first requirement of each distinct one
+  std::vector<int> path_of(reqs.size(), -1);
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    const Require& r = reqs[k];
+    if (r.path.size() > JG_PATH_MAX_COMP) usable = false;
+    for (const std::string& comp : r.path) {
+      if (comp.empty() || comp.size() > JG_SELECT_NAME_MAX) usable = false;
+      for (unsigned char c : comp)
+        if (!scan_byte_ok(c)) usable = false;
+    }
+    // Present ignores its value on both paths
+    const size_t vlen = r.op == Require::Present ? 0 : r.value.size();
+    if (vlen > JG_PRED_VALUE_MAX) usable = false;
+    if ((r.op == Require::HasWord || r.op == Require::HasElement) && vlen == 0) usable = false;
+    for (size_t b = 0; b < vlen; ++b)
+      if (!scan_byte_ok((unsigned char)r.value[b]) || (r.op == Require::HasWord && r.value[b] == ' ')) usable = false;
+    size_t u = 0;
+    while (u < upaths.size() && *upaths[u] != r.path) ++u;
+    if (u == upaths.size()) upaths.push_back(&r.path);
+    path_of[k] = (int)u;
+    size_t q = 0;
+    for (; q < upreds.size(); ++q) {
+      const Require& o = reqs[upreds[q]];
+      if (path_of[upreds[q]] == path_of[k] && o.op == r.op && (r.op == Require::Present || o.value == r.value)) break;
+    }
+    if (q == upreds.size()) upreds.push_back(k);
+    bit[k] = (int)q;
+    identity = identity && q == k;
+  }
+  if (upaths.size() > JG_MAX_PATHS) usable = false;
+  if (!usable) return;
+  for (size_t u = 0; u < upaths.size(); ++u) {
+    paths.ncomp[u] = (uint32_t)upaths[u]->size();
+    for (size_t d = 0; d < upaths[u]->size(); ++d) {
+      paths.comp_len[u][d] = (uint32_t)(*upaths[u])[d].size();
+      names += (*upaths[u])[d];
+    }
+  }
+  paths.n = (uint32_t)upaths.size();
+  paths.names = (const uint8_t*)names.data();
+  for (size_t q = 0; q < upreds.size(); ++q) {
+    const Require& r = reqs[upreds[q]];
+    preds.path[q] = (uint8_t)path_of[upreds[q]];
+    preds.op[q] = (uint8_t)r.op;
+    preds.value_len[q] = r.op == Require::Present ? 0u : (uint32_t)r.value.size();
+    if (r.op != Require::Present) values += r.value;
+  }
+  preds.n = (uint32_t)upreds.size();
+  preds.values = (const uint8_t*)values.data();
+}
+}  // namespace
+
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs) {
+  check_requires(reqs);
+  uint32_t bits = 0;
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    const Require& r = reqs[k];
+    // the claims map walked along the path: every value on the way an object that holds the key
+    const json::Value* v = &all_claims;
+    for (const std::string& comp : r.path) {
+      if (v->kind != json::Value::Object) { v = nullptr; break; }
+      v = v->get(comp);
+      if (!v) break;
+    }
+    if (!v) continue;
+    bool hit = false;
+    switch (r.op) {
+      case Require::Present: hit = true; break;
+      case Require::Equals: hit = v->kind == json::Value::String && v->str.view() == r.value; break;
+      case Require::HasWord:
+        if (v->kind == json::Value::String) {        // strings.Split(v, " "): only 0x20 separates, empty pieces count
+          const std::string_view s = v->str.view();
+          size_t at = 0;
+          for (;;) {
+            const size_t sp = s.find(' ', at);
+            const std::string_view piece = s.substr(at, sp == std::string_view::npos ? std::string_view::npos : sp - at);
+            if (piece == r.value) { hit = true; break; }
+            if (sp == std::string_view::npos) break;
+            at = sp + 1;
+          }
+        }
+        break;
+      case Require::HasElement:
+        if (v->kind == json::Value::Array)
+          for (const json::Value& e : v->arr)
+            if (e.kind == json::Value::String && e.str.view() == r.value) { hit = true; break; }
+        break;
+    }
+    if (hit) bits |= 1u << k;
+  }
+  return bits;
+}
+
+std::vector<MatchResult> Validator::MatchBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                               const std::vector<Require>& requires_, CheckStats* stats) {
+  const MatchPlan plan(requires_);
+  std::vector<MatchResult> out(tokens.size());
+  check_core<kMatchMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
+                                [&](size_t i, bool ok, std::string&& err, uint32_t bits) {
+                                  out[i].ok = ok;
+                                  out[i].err = std::move(err);
+                                  out[i].bits = bits;
+                                }, nullptr, nullptr, &plan);
+  return out;
+}
+
+void Validator::MatchVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
+                              const std::vector<Require>& requires_, uint8_t* ok_out, uint32_t* bits_out,
+                              CheckStats* stats) {
+  const MatchPlan plan(requires_);
+  check_core<kMatchMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
+                                [&](size_t i, bool ok, std::string&&, uint32_t bits) {
+                                  ok_out[i] = ok ? 1 : 0;
+                                  bits_out[i] = bits;
+                                }, nullptr, nullptr, &plan);
+}
+
+std::vector<MatchResult> Validator::MatchBatchEach(const std::vector<std::string_view>& tokens,
+                                                   const std::vector<Expected>& expected,
+                                                   const std::vector<uint32_t>& which,
+                                                   const std::vector<Require>& requires_, CheckStats* stats) {
+  each_args("MatchBatchEach", tokens, expected, which);
+  const MatchPlan plan(requires_);
+  std::vector<MatchResult> out(tokens.size());
+  check_core<kMatchMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                               [&](size_t i, bool ok, std::string&& err, uint32_t bits) {
+                                 out[i].ok = ok;
+                                 out[i].err = std::move(err);
+                                 out[i].bits = bits;
+                               }, nullptr, nullptr, &plan);
+  return out;
+}
+
+void Validator::MatchVerdictsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                                  const std::vector<uint32_t>& which, const std::vector<Require>& requires_,
+                                  uint8_t* ok_out, uint32_t* bits_out, CheckStats* stats) {
+  each_args("MatchVerdictsEach", tokens, expected, which);
+  const MatchPlan plan(requires_);
+  check_core<kMatchMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                               [&](size_t i, bool ok, std::string&&, uint32_t bits) {
+                                 ok_out[i] = ok ? 1 : 0;
+                                 bits_out[i] = bits;
+                               }, nullptr, nullptr, &plan);
+}
+
 // The claims entries are the ones the host layer binds weakly: an ABI provider
 // without them (the stub ABI the CPU unit tests link, an older libcapjwt.so)
 // still links, and a CheckBatch against it reports the scan as unavailable, as
 // any other device failure.  jg_claims_scan (CheckBatch), jg_claims_extract
 // (RegisteredBatch), jg_claims_select (SelectBatch), jg_claims_each (the *Each
-// entries: the three scans with a profile per job) and jg_claims_paths (the
-// Select entries by path).
+// entries: the three scans with a profile per job), jg_claims_paths (the
+// Select entries by path) and jg_claims_match (the Match entries).
 extern "C" {
 __attribute__((weak)) int jg_claims_scan(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                          uint8_t*);
@@ -2765,6 +2970,8 @@ __attribute__((weak)) int jg_claims_each(jg_ctx*, const uint8_t*, size_t, const 
                                          uint32_t, const jg_select*, uint8_t*, jg_claims*, jg_selected*);
 __attribute__((weak)) int jg_claims_paths(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                           uint32_t, const jg_paths*, uint8_t*, jg_claims*, jg_selected*);
+__attribute__((weak)) int jg_claims_match(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                          uint32_t, const jg_paths*, const jg_preds*, uint8_t*, uint32_t*);
 }
 
 void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
@@ -2805,6 +3012,15 @@ void Engine::claims_paths(const uint8_t* arena, size_t arena_len, const void* jo
   abi_call("jg_claims_paths", jg_claims_paths != nullptr, inside_verify, [&] {
     return jg_claims_paths(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
                            (const jg_paths*)paths, codes, (jg_claims*)vals, (jg_selected*)sels);
+  });
+}
+
+void Engine::claims_match(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                          uint32_t nexpect, const void* paths, const void* preds, uint8_t* codes, uint32_t* masks,
+                          bool inside_verify) {
+  abi_call("jg_claims_match", jg_claims_match != nullptr, inside_verify, [&] {
+    return jg_claims_match(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                           (const jg_paths*)paths, (const jg_preds*)preds, codes, masks);
   });
 }
 

@@ -214,6 +214,11 @@ class Engine {
   void claims_paths(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                     uint32_t nexpect, const void* paths, uint8_t* codes, void* vals, void* sels,
                     bool inside_verify = false);
+  // jg_claims_each's codes and masks[i] = the predicates of `preds` (a jg_preds
+  // over `paths`, a jg_paths) that hold on job i's claims (jg_claims_match)
+  void claims_match(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                    uint32_t nexpect, const void* paths, const void* preds, uint8_t* codes, uint32_t* masks,
+                    bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -499,6 +504,30 @@ using ClaimPath = std::vector<std::string>;
 struct ClaimPaths {
   std::vector<ClaimPath> paths;
 };
+// A yes/no question about one claim (MatchBatch).  With v the value the claims
+// map holds at `path`:
+//   Equals      v is a string equal to `value` ("" allowed)
+//   HasWord     v is a string and one of strings.Split(v, " ") equals `value`
+//               (the RFC 6749 scope form)
+//   HasElement  v is an array and one of its direct elements is a string equal
+//               to `value`
+//   Present     the path reaches a value (null counts); `value` is unused
+// The numbers are jg_pred_op's (include/jg.h).
+struct Require {
+  enum Op : uint8_t { Equals = 1, HasWord = 2, HasElement = 3, Present = 4 };
+  ClaimPath path;
+  Op op = Present;
+  std::string value;
+};
+// At most this many per call: the mask has one bit per requirement (JG_MAX_PRED)
+constexpr size_t kMaxRequires = 16;
+// CheckBatch's (ok, error string) and, for an accepted token, bit k set when
+// requires[k] holds on its claims.  A rejected token carries no bits.
+struct MatchResult {
+  bool ok = false;
+  std::string err;
+  uint32_t bits = 0;
+};
 // SelectBatch as columns (SelectBlob): RegisteredColumns plus, per name, the
 // value's type, its number and its text.  Rows of a rejected token are empty.
 struct SelectColumns {
@@ -618,6 +647,34 @@ class Validator {
   void SelectColsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
                       const std::vector<uint32_t>& which, const ClaimPaths& paths,
                       const SelectColumns& out, CheckStats* stats = nullptr);
+  // CheckBatch plus yes/no questions about claims, answered where the bytes are:
+  // ok / err are CheckBatch's, token for token, and bit k of an accepted token's
+  // bits says whether requires[k] holds on ValidateBatch's claims map for it (the
+  // value reached as the Select entries' paths reach it).  The scan compares the
+  // values while it walks the payload (jg_claims_match) and returns four bytes per
+  // token: no span, no merge of text, no column.  A requirement never changes ok
+  // or err.  A token the scan leaves to the host evaluates the same requirements
+  // on its verified claims map (match_requires).  A list the scan does not take
+  // (more than JG_MAX_PATHS distinct paths, a path of more than JG_PATH_MAX_COMP
+  // components, a component or a value with a byte it refuses, a value over
+  // JG_PRED_VALUE_MAX bytes, an empty value or one with a space for HasWord, an
+  // empty value for HasElement) sends every token to the host path, so results do
+  // not depend on the caps; equal requirements are scanned once.  Throws
+  // std::invalid_argument for more than kMaxRequires requirements, a path without
+  // components, a component or a value with a NUL byte, and an unknown op.
+  std::vector<MatchResult> MatchBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                      const std::vector<Require>& requires_, CheckStats* stats = nullptr);
+  // MatchBatch's accept bits and masks alone (MatchBlob): ok[i] is 1 when Validate
+  // returns no error, bits[i] the mask (0 for a rejected token); n entries each
+  void MatchVerdicts(const std::vector<std::string_view>& tokens, const Expected& expected,
+                     const std::vector<Require>& requires_, uint8_t* ok, uint32_t* bits, CheckStats* stats = nullptr);
+  // ... and with an Expected per token, as the *Each entries above
+  std::vector<MatchResult> MatchBatchEach(const std::vector<std::string_view>& tokens,
+                                          const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
+                                          const std::vector<Require>& requires_, CheckStats* stats = nullptr);
+  void MatchVerdictsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                         const std::vector<uint32_t>& which, const std::vector<Require>& requires_, uint8_t* ok,
+                         uint32_t* bits, CheckStats* stats = nullptr);
  private:
   KeySet* ks_;
 };
@@ -634,6 +691,10 @@ Result validate_claims(const json::Value& all_claims, const TokenView& info, con
 // claims map unmarshals, whatever the checks then say)
 Result validate_claims(const json::Value& all_claims, const TokenView& info, const Expected& expected,
                        int64_t now_unix_ns, RegisteredClaims* decoded);
+// The requirements of a MatchBatch call on a verified claims map: bit k set
+// when requires[k] holds.  What the host path of MatchBatch runs; exposed for
+// tests.  Throws as MatchBatch does.
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& requires_);
 // Expected's three leeways after Go's defaulting (jwt/jwt.go:128-170): the
 // clock skew in ns (negative -> 0, 0 -> one minute) and the leeways that
 // default a missing exp / nbf, as the whole seconds Go adds (negative -> 0,

@@ -382,6 +382,15 @@ PYBIND11_MODULE(_capjwt_host, m) {
     if (r.ok) r.claims = v;
     return result_py(r);
   });
+  m.def("match_requires", [](py::bytes payload, const std::vector<std::tuple<ClaimPath, int, std::string>>& reqs) {
+    // the host path of MatchBatch on a payload whose claims were accepted: the mask
+    json::Value v;
+    std::string err;
+    if (!json::parse(std::string(payload), &v, &err)) throw py::value_error(err);
+    std::vector<Require> rq;
+    for (const auto& [path, op, value] : reqs) rq.push_back(Require{path, (Require::Op)op, value});
+    return match_requires(v, rq);
+  });
   m.def("host_threads", &host_threads);
   m.def("set_host_memory_retention", &SetHostMemoryRetention);
   m.def("trim_host_memory", &TrimHostMemory);
@@ -646,6 +655,64 @@ PYBIND11_MODULE(_capjwt_host, m) {
     d["sel"] = sel;
     return py::make_tuple(d, st.scanned, st.host);
   };
+  // a requirement as Python hands it over: (path, op, value)
+  using ReqList = std::vector<std::tuple<ClaimPath, int, std::string>>;
+  auto requires_of = [](const ReqList& reqs) {
+    std::vector<Require> rq;
+    rq.reserve(reqs.size());
+    for (const auto& [path, op, value] : reqs) rq.push_back(Require{path, (Require::Op)op, value});
+    return rq;
+  };
+  auto py_match_batch = [=](PyValidator& s, py::sequence toks, const ReqList& reqs, const Who& who) {
+    // check_batch with the requirements' mask: ([(bits or None, error or None)], scanned, host)
+    auto v = as_strings(toks);
+    const std::vector<Require> rq = requires_of(reqs);
+    std::vector<MatchResult> rs;
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      rs = who.es ? s.v->MatchBatchEach(views(v), *who.es, *who.w, rq, &st) : s.v->MatchBatch(views(v), *who.e, rq, &st);
+    }
+    py::list out(rs.size());
+    for (size_t i = 0; i < rs.size(); ++i) {
+      if (rs[i].ok) out[i] = py::make_tuple(py::int_(rs[i].bits), py::none());
+      else out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
+    }
+    return py::make_tuple(out, st.scanned, st.host);
+  };
+  auto py_match_blob = [=](PyValidator& s, py::bytes blob, const ReqList& reqs, const Who& who) {
+    // check_blob with a uint32 mask column: newline-separated tokens in,
+    // ({"ok": accept bytes, "match": masks}, scanned, host) out -- no strings
+    char* bp = nullptr;
+    Py_ssize_t bn = 0;
+    if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+    const std::vector<Require> rq = requires_of(reqs);
+    const bool trace = std::getenv("CAPJWT_TRACE") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+      if (!trace) return;
+      const auto t1 = std::chrono::steady_clock::now();
+      std::fprintf(stderr, "[capjwt] mblob %-12s %8.2f ms\n", what,
+                   std::chrono::duration<double, std::milli>(t1 - t0).count());
+      t0 = t1;
+    };
+    auto toks = split_lines(bp, (size_t)bn);
+    lap("split");
+    py::bytes ok = fresh_bytes(toks.size()), match = fresh_bytes(4 * toks.size());
+    uint8_t* const okp = (uint8_t*)bytes_mem(ok);
+    uint32_t* const mp = (uint32_t*)bytes_mem(match);
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      if (who.es) s.v->MatchVerdictsEach(toks, *who.es, *who.w, rq, okp, mp, &st);
+      else s.v->MatchVerdicts(toks, *who.e, rq, okp, mp, &st);
+    }
+    lap("match");
+    py::dict d;
+    d["ok"] = ok;
+    d["match"] = match;
+    return py::make_tuple(d, st.scanned, st.host);
+  };
   py::class_<PyValidator>(m, "Validator")
       .def(py::init([](PyKeySet* ks) {
         if (!ks) throw py::value_error("keySet must not be nil");
@@ -762,6 +829,21 @@ PYBIND11_MODULE(_capjwt_host, m) {
                                        const std::vector<Expected>& es, py::buffer which) {
         const std::vector<uint32_t> w = which_of(which);
         return py_select_blob(s, blob, paths, Who{nullptr, &es, &w});
+      })
+      .def("match_batch", [=](PyValidator& s, py::sequence toks, ReqList reqs, const Expected& e) {
+        return py_match_batch(s, toks, reqs, Who{&e, nullptr, nullptr});
+      })
+      .def("match_batch_each", [=](PyValidator& s, py::sequence toks, ReqList reqs,
+                                 const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
+        return py_match_batch(s, toks, reqs, Who{nullptr, &es, &which});
+      })
+      .def("match_blob", [=](PyValidator& s, py::bytes blob, ReqList reqs, const Expected& e) {
+        return py_match_blob(s, blob, reqs, Who{&e, nullptr, nullptr});
+      })
+      .def("match_blob_each", [=](PyValidator& s, py::bytes blob, ReqList reqs,
+                                const std::vector<Expected>& es, py::buffer which) {
+        const std::vector<uint32_t> w = which_of(which);
+        return py_match_blob(s, blob, reqs, Who{nullptr, &es, &w});
       })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {

@@ -719,6 +719,7 @@ struct Device {
   Grow cl_select, cl_sel;           // jg_claims_select's resolved names and its records
   Grow cl_profiles;                 // jg_claims_each's resolved table
   Grow cl_paths;                    // jg_claims_paths' resolved paths
+  Grow cl_preds, cl_match;          // jg_claims_match's resolved predicates and its masks
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -3468,7 +3469,7 @@ int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
 
 namespace {
 
-// One scan of the claims: what the five jg_claims_* entries hand to claims_run.
+// One scan of the claims: what the six jg_claims_* entries hand to claims_run.
 // The resolved sides are host objects that `resolve` fills and points these at;
 // each is uploaded into the kept device buffer of its kind, and the kernel is
 // picked from which of them, and which outputs, are there (launch_claims).
@@ -3484,6 +3485,8 @@ struct ClaimsCall {
   const jgclaims::Profiles* table = nullptr;    // or name one of the table's profiles
   const jgclaims::Select* select = nullptr;     // at most one of these two, with sel_out
   const jgclaims::Paths* paths = nullptr;
+  const jgclaims::Preds* preds = nullptr;       // with paths and match_out: the masks in the place of the records
+  uint32_t* match_out = nullptr;
 };
 
 const char kRefuseExpect[] = "more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9";
@@ -3496,6 +3499,11 @@ const char kRefuseSelect[] =
 const char kRefusePaths[] =
     "more than 8 paths, a path of no or more than 4 components, a component that is "
     "empty, over 64 bytes or not printable ASCII without quote and backslash, or two equal paths";
+
+const char kRefusePreds[] =
+    "more than 16 predicates, a path index past the paths, an unknown op, a value that is "
+    "over 64 bytes, empty for HAS_WORD or HAS_ELEMENT, not empty for PRESENT or not printable "
+    "ASCII without quote and backslash, a space in a HAS_WORD value, or two identical predicates";
 
 // The one path of a scan, after the entry's own NULL-argument test.  `resolve`
 // is the entry's resolve step: it fills the call's resolved sides and returns
@@ -3546,11 +3554,16 @@ int claims_run(jg_ctx* ctx, const std::string& entry, ClaimsCall& c, const std::
     L.code_out = (uint8_t*)d->cl_out.get(njobs);
     if (c.vals_out) L.vals_out = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
     if (c.sel_out) L.sel_out = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
+    if (c.match_out) {
+      L.preds = (const jgclaims::Preds*)upload(d->cl_preds, c.preds, sizeof *c.preds);
+      L.match_out = (uint32_t*)d->cl_match.get(sizeof(uint32_t) * njobs);
+    }
     launch_claims(L, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c.code_out, L.code_out, njobs, hipMemcpyDeviceToHost, s));
     if (c.vals_out) HIPCHK(hipMemcpyAsync(c.vals_out, L.vals_out, sizeof(jg_claims) * njobs, hipMemcpyDeviceToHost, s));
     if (c.sel_out) HIPCHK(hipMemcpyAsync(c.sel_out, L.sel_out, sizeof(jg_selected) * njobs, hipMemcpyDeviceToHost, s));
+    if (c.match_out) HIPCHK(hipMemcpyAsync(c.match_out, L.match_out, sizeof(uint32_t) * njobs, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
   } catch (const std::exception& e) {
@@ -3642,6 +3655,30 @@ int jg_claims_paths(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     if (!jgclaims::resolve_paths(*paths, P.get())) return kRefusePaths;
     c.table = T.get();
     c.paths = P.get();
+    return nullptr;
+  });
+}
+
+// jg_claims_paths' matcher with predicates on what the paths reach: two small
+// uploads (the resolved paths and predicates) and four bytes per token back
+int jg_claims_match(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                    const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
+                    const jg_paths* paths, const jg_preds* preds, uint8_t* code_out, uint32_t* match_out) {
+  if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out || !paths || !preds || !match_out)) ||
+      (arena_len > 0 && !arena))
+    return -1;
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, nullptr, nullptr};
+  auto T = std::make_unique<jgclaims::Profiles>();
+  auto P = std::make_unique<jgclaims::Paths>();
+  auto Q = std::make_unique<jgclaims::Preds>();
+  return claims_run(ctx, "jg_claims_match", c, [&]() -> const char* {
+    if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) return kRefuseProfiles;
+    if (!jgclaims::resolve_paths(*paths, P.get())) return kRefusePaths;
+    if (!jgclaims::resolve_preds(*preds, *P, Q.get())) return kRefusePreds;
+    c.table = T.get();
+    c.paths = P.get();
+    c.preds = Q.get();
+    c.match_out = match_out;
     return nullptr;
   });
 }

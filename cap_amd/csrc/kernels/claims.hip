@@ -61,7 +61,7 @@ __device__ __forceinline__ void store_selected(jg_selected* out, const jg_select
                     q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
 }
 
-// The body of all seven kernels.  M is the scan's mode.  X is the block's LDS
+// The body of all eight kernels.  M is the scan's mode.  X is the block's LDS
 // copy of the expected side, XS its type:
 //   Expect    one for the call, copied whole;
 //   Profiles  the call's table (jg_claims_each), copied only as far as it is in
@@ -71,13 +71,16 @@ __device__ __forceinline__ void store_selected(jg_selected* out, const jg_select
 //             which only makes the base of the LDS reads per-lane (their
 //             addresses depend on the lane's position in its value already).
 // S is the LDS copy of what a selecting mode selects by, SL its type: Select's
-// names or, for kPath, Paths.  The records stay in registers (fields and
-// constant indices only) until they are stored.
+// names or, for kPath and kMatch, Paths.  The records stay in registers (fields
+// and constant indices only) until they are stored.  Q is the LDS copy of the
+// predicates of kMatch, which keeps no record: a byte and a dword per lane.
 template <int M, class XS, class SL>
 __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restrict__ arena,
                                             const jg_cjob* __restrict__ jobs, int64_t n, const XS* __restrict__ expect,
                                             const SL* __restrict__ select, uint8_t* __restrict__ code_out,
-                                            jg_claims* __restrict__ vals_out, jg_selected* __restrict__ sel_out) {
+                                            jg_claims* __restrict__ vals_out, jg_selected* __restrict__ sel_out,
+                                            Preds* Q = nullptr, const Preds* __restrict__ preds = nullptr,
+                                            uint32_t* __restrict__ match_out = nullptr) {
   constexpr bool kTable = std::is_same_v<XS, Profiles>;
   uint32_t np = 0;
   if constexpr (kTable) {
@@ -93,6 +96,7 @@ __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restr
     copy_words(&X, expect, 0u, sizeof(Expect) / 4u);
   }
   if constexpr (M >= kSelect) copy_words(S, select, 0u, sizeof(SL) / 4u);
+  if constexpr (M == kMatch) copy_words(Q, preds, 0u, sizeof(Preds) / 4u);
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -103,14 +107,16 @@ __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restr
   src.cur = src.aligned[0];
   jg_claims v;
   jg_selected q;
+  uint32_t bits;
   if constexpr (kTable) {
     const ProfileRef E{X, J.flags < np ? J.flags : 0u};                         // likewise: checked before the launch
-    code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q);
+    code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q, Q, &bits);
   } else {
     code_out[i] = scan_segment<M>(src, J.len, X, &v, S, &q);
   }
-  if constexpr (M >= kExtract) store_claims(vals_out + i, v);
-  if constexpr (M >= kSelect) store_selected(sel_out + i, q);
+  if constexpr (kRec<M>) store_claims(vals_out + i, v);
+  if constexpr (kSel<M>) store_selected(sel_out + i, q);
+  if constexpr (M == kMatch) match_out[i] = bits;
 }
 
 // code_out[i] = the jg_claim_code of jobs[i]
@@ -195,6 +201,25 @@ __global__ void __launch_bounds__(kBlock) k_claims_paths_each(const uint8_t* __r
   claims_body<kPath, Profiles, Paths>(T, &P, arena, jobs, n, table, paths, code_out, vals_out, sel_out);
 }
 
+// k_claims_scan_each that also answers the caller's predicates on members
+// reached by path (jg_claims_match): the resolved paths and predicates sit in LDS
+// beside the table; keys are matched as in k_claims_paths_each, and the value a
+// path reaches is compared from LDS with the values of the predicates on that
+// path.  match_out[i] is the mask of the predicates that hold; no record is kept.
+__global__ void __launch_bounds__(kBlock) k_claims_match_each(const uint8_t* __restrict__ arena,
+                                                              const jg_cjob* __restrict__ jobs, int64_t n,
+                                                              const Profiles* __restrict__ table,
+                                                              const Paths* __restrict__ paths,
+                                                              const Preds* __restrict__ preds,
+                                                              uint8_t* __restrict__ code_out,
+                                                              uint32_t* __restrict__ match_out) {
+  __shared__ Profiles T;
+  __shared__ Paths P;
+  __shared__ Preds Q;
+  claims_body<kMatch, Profiles, Paths>(T, &P, arena, jobs, n, table, paths, code_out, nullptr, nullptr, &Q, preds,
+                                       match_out);
+}
+
 }  // namespace
 
 void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
@@ -203,7 +228,8 @@ void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
   const auto go = [&](auto kernel, auto... rest) {
     hipLaunchKernelGGL(kernel, grid, block, 0, s, c.arena, c.jobs, c.n, rest...);
   };
-  if (c.paths) go(k_claims_paths_each, c.table, c.paths, c.code_out, c.vals_out, c.sel_out);
+  if (c.match_out) go(k_claims_match_each, c.table, c.paths, c.preds, c.code_out, c.match_out);
+  else if (c.paths) go(k_claims_paths_each, c.table, c.paths, c.code_out, c.vals_out, c.sel_out);
   else if (c.table && c.sel_out) go(k_claims_select_each, c.table, c.select, c.code_out, c.vals_out, c.sel_out);
   else if (c.table && c.vals_out) go(k_claims_extract_each, c.table, c.code_out, c.vals_out);
   else if (c.table) go(k_claims_scan_each, c.table, c.code_out);

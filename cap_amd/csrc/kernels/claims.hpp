@@ -36,6 +36,13 @@
 // beside the profile table): component j is matched at depth j inside the object
 // that components 1..j-1 opened.
 //
+// claims_match_each() is a fifth mode (ScanT<kMatch>): the path matcher of
+// kPath without any record, and in the place of the spans a mask of the
+// caller's predicates (Preds, in LDS beside the paths) that hold on the values
+// the paths reach: a candidate mask over the predicates' values is armed by the
+// value's first byte, narrowed per byte and resolved at the closing quote, as
+// `cand` is for the expected strings.
+//
 // The expected side is a template parameter of the scan (EX: slen / sbyte / auds
 // and the window's edges).  Expect is one; ProfileRef, one profile of a
 // Profiles table picked per token, is the other: claims_decide_each,
@@ -282,6 +289,69 @@ inline bool resolve_paths(const jg_paths& x, Paths* P) {
   return true;
 }
 
+// The caller's predicates as the matching scan reads them (a device buffer
+// copied to LDS beside the profile table and the paths).  Masks over the
+// predicates hold predicate k at bit k.  Per path: every predicate on it -- what a
+// member that replaces the path's value clears -- and those the first byte of its
+// value arms, split by operator.
+struct Preds {
+  uint32_t n;
+  uint16_t all[JG_MAX_PATHS];                         // every predicate on the path
+  uint16_t present[JG_MAX_PATHS];                     // PRESENT: set when the value begins
+  uint16_t str[JG_MAX_PATHS];                         // EQUALS and HAS_WORD: armed by a string
+  uint16_t word[JG_MAX_PATHS];                        // HAS_WORD alone: armed again after a space
+  uint16_t elem[JG_MAX_PATHS];                        // HAS_ELEMENT: armed by a string element of the array
+  uint8_t op[JG_MAX_PRED];
+  uint8_t len[JG_MAX_PRED];
+  uint16_t off[JG_MAX_PRED];                          // into pool
+  uint8_t pool[JG_MAX_PRED * JG_PRED_VALUE_MAX];
+};
+static_assert(sizeof(Preds) == 4 + 5 * 16 + 16 + 16 + 32 + 1024, "no padding in the predicates");
+static_assert(JG_MAX_PRED <= 16 && JG_PRED_VALUE_MAX <= 255, "a 16-bit mask per path, a byte per length");
+
+// Fills *Q from the ABI's jg_preds, for the resolved paths P of the same call.
+// False: more than JG_MAX_PRED predicates, a path index past P.n, an unknown
+// operator, a length outside the operator's range (EQUALS 0..JG_PRED_VALUE_MAX,
+// HAS_WORD and HAS_ELEMENT 1..JG_PRED_VALUE_MAX, PRESENT 0), a value byte
+// name_byte_ok() refuses, a space in a HAS_WORD value, two identical predicates.
+inline bool resolve_preds(const jg_preds& x, const Paths& P, Preds* Q) {
+  if (x.n > JG_MAX_PRED) return false;
+  *Q = Preds{};
+  uint8_t path[JG_MAX_PRED] = {};
+  uint32_t o = 0;
+  for (uint32_t k = 0; k < x.n; ++k) {
+    const uint32_t p = x.path[k], op = x.op[k], l = x.value_len[k];
+    if (p >= P.n || op < JG_PRED_EQUALS || op > JG_PRED_PRESENT) return false;
+    const uint32_t lo = op == JG_PRED_EQUALS || op == JG_PRED_PRESENT ? 0u : 1u;
+    const uint32_t hi = op == JG_PRED_PRESENT ? 0u : (uint32_t)JG_PRED_VALUE_MAX;
+    if (l < lo || l > hi || (l && !x.values)) return false;
+    for (uint32_t b = 0; b < l; ++b) {
+      const uint8_t c = x.values[o + b];
+      if (!name_byte_ok(c) || (op == JG_PRED_HAS_WORD && c == 0x20u)) return false;
+      Q->pool[o + b] = c;
+    }
+    path[k] = (uint8_t)p;
+    Q->op[k] = (uint8_t)op;
+    Q->len[k] = (uint8_t)l;
+    Q->off[k] = (uint16_t)o;
+    for (uint32_t j = 0; j < k; ++j) {
+      if (path[j] != p || Q->op[j] != op || Q->len[j] != l) continue;
+      uint32_t b = 0;
+      while (b < l && Q->pool[Q->off[j] + b] == Q->pool[o + b]) ++b;
+      if (b == l) return false;
+    }
+    const uint16_t bit = (uint16_t)(1u << k);
+    Q->all[p] |= bit;
+    if (op == JG_PRED_PRESENT) Q->present[p] |= bit;
+    if (op == JG_PRED_EQUALS || op == JG_PRED_HAS_WORD) Q->str[p] |= bit;
+    if (op == JG_PRED_HAS_WORD) Q->word[p] |= bit;
+    if (op == JG_PRED_HAS_ELEMENT) Q->elem[p] |= bit;
+    o += l;
+  }
+  Q->n = x.n;
+  return true;
+}
+
 enum : uint32_t {
   ST_START, ST_VALUE, ST_ARR_FIRST, ST_OBJ_FIRST, ST_OBJ_KEY, ST_COLON, ST_AFTER, ST_STR,
   ST_NUM_MINUS, ST_NUM_ZERO, ST_NUM_INT, ST_NUM_DOT, ST_NUM_FRAC, ST_LIT, ST_DONE
@@ -334,13 +404,36 @@ struct PathState {
 };
 struct ExtractPath : Extract, SelState, PathState {};
 
+// What the matching form (claims_match_each) keeps: the path matcher's state
+// without any record (no span is latched, so no decoded position either), and
+// the predicates.  mcand is `cand` for the predicates' values: bit k means value k
+// still equals the string read so far (EQUALS, HAS_ELEMENT: at ScanT::pos) or
+// its current word (HAS_WORD: at wpos).  One open string and one open array are
+// enough: a path never descends into an array, so no key inside the open one
+// selects anything until it closes, and an object that a shorter path selects
+// around the open value can only carry PRESENT, which is decided when it begins.
+struct MatchState {
+  uint32_t kcand = 0, md = 0, desc = 0, kselv = 0;    // as SelState's and PathState's
+  uint32_t mcand = 0;               // predicates whose value the open string, or its current word, can still be
+  uint32_t mword = 0;               // the HAS_WORD predicates of the open string: a space arms them again
+  uint32_t wpos = 0;                // the position inside the current word
+  uint32_t marr = 0, medepth = 0;   // slot + 1 of the selected array that is open; the depth of its direct elements
+  uint32_t res = 0;                 // the predicates that hold on what was read so far
+};
+
 // The scan's compile-time modes: the verdict alone, with the jg_claims record,
-// and with the record and the caller's selected members (jg_selected)
-constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3;
+// with the record and the caller's selected members (jg_selected) by name or by
+// path, and with the caller's predicates on members reached by path
+constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3, kMatch = 4;
+// what a mode keeps: the jg_claims record, the jg_selected record, the path matcher
+template <int M> constexpr bool kRec = M >= kExtract && M <= kPath;
+template <int M> constexpr bool kSel = M >= kSelect && M <= kPath;
+template <int M> constexpr bool kWalk = M == kPath || M == kMatch;
 
 template <int M>
-struct ScanT : std::conditional_t<M == kPath, ExtractPath, std::conditional_t<M == kSelect, ExtractSelect,
-                                  std::conditional_t<M == kExtract, Extract, NoExtract>>> {
+struct ScanT : std::conditional_t<M == kMatch, MatchState, std::conditional_t<M == kPath, ExtractPath,
+                                  std::conditional_t<M == kSelect, ExtractSelect,
+                                  std::conditional_t<M == kExtract, Extract, NoExtract>>>> {
   uint32_t st = ST_START;
   uint32_t depth = 0, stk = 0;      // open containers; bit d: container d+1 is an object
   uint32_t field = F_NONE;          // the top-level member whose value comes next
@@ -456,28 +549,48 @@ template <int M>
 JG_CL_HD void pop(ScanT<M>& s, uint32_t is_obj) {
   if (((s.stk >> (s.depth - 1u)) & 1u) != is_obj) { s.bad = 1; return; }
   --s.depth;
-  if constexpr (M >= kExtract) s.aud_len = s.depth == 1u && s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud's ]
+  if constexpr (kRec<M>) s.aud_len = s.depth == 1u && s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud's ]
   if (s.depth == 1u) s.aud_arr = 0;
-  if constexpr (M == kPath) {
+  if constexpr (kWalk<M>) {
     // a matched object closed: the paths that were inside it (field == depth) are one component back
     if (s.depth - 1u < 3u) {
       const uint32_t x = s.md ^ (s.depth * 0x5555u);
       s.md -= ~(x | (x >> 1)) & 0x5555u;
     }
   }
-  if constexpr (M >= kSelect) sel_end(s, s.dpos + 1u, 0u);        // the selected member's ] or }
+  if constexpr (kSel<M>) sel_end(s, s.dpos + 1u, 0u);          // the selected member's ] or }
+  if constexpr (M == kMatch) s.marr = s.depth < s.medepth ? 0u : s.marr;   // the selected array's ]
   end_value(s);
 }
 
 // the first byte of a value
 template <int M, class EX>
-JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
+JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const Preds* Q = nullptr) {
+  (void)Q;
   const uint32_t f = s.depth == 1u ? s.field : (uint32_t)F_NONE;
   const uint32_t elem = s.depth == 2u && s.aud_arr;        // an element of aud's array
   const uint32_t is_str3 = f - F_ISS < 3u, is_date = f - F_EXP < 3u;
-  if constexpr (M == kPath) {                          // only an object is descended into
+  if constexpr (kWalk<M>) {                            // only an object is descended into
     s.md += c == '{' ? s.desc : 0u;
     s.desc = 0;
+  }
+  if constexpr (M == kMatch) {
+    // The value of the member a path ends at (its key cleared the path's predicates), or a direct
+    // element of that member's open array: PRESENT holds from here; a string arms the candidates.
+    const uint32_t slot = path_slot(s);
+    const uint32_t el = s.marr && s.depth == s.medepth ? s.marr : 0u;
+    const bool str = c == '"';
+    if (slot) {
+      s.kselv &= ~(0xfu << (4u * (s.depth - 1u)));     // the member is read: an array's elements at this depth have no key
+      s.res |= Q->present[slot - 1u];
+    }
+    s.mcand = !str ? 0u : slot ? Q->str[slot - 1u] : el ? Q->elem[el - 1u] : 0u;
+    s.mword = str && slot ? Q->word[slot - 1u] : 0u;
+    s.wpos = 0;
+    if (c == '[' && slot) {
+      s.marr = slot;
+      s.medepth = s.depth + 1u;
+    }
   }
   if (c == '"') {
     if (is_date) s.bad = 1;
@@ -488,7 +601,7 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
     s.cmpf = elem ? (uint32_t)F_AUD : f;
     s.cand = is_str3 ? (E.slen(f - 1u) ? 1u << (f - 1u) : 0u)
            : (f == F_AUD || elem) ? ((1u << E.auds()) - 1u) << 3 : 0u;
-    if constexpr (M >= kExtract) {
+    if constexpr (kRec<M>) {
       const uint32_t in = s.dpos + 1u;                 // the first byte between the quotes
       s.iss_off = f == F_ISS ? in : s.iss_off;
       s.sub_off = f == F_SUB ? in : s.sub_off;
@@ -497,16 +610,16 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
       s.aud_n = f == F_AUD ? 1u : s.aud_n + elem;
       s.present |= (is_str3 || f == F_AUD) ? 1u << f : 0u;
     }
-    if constexpr (M >= kSelect) {
+    if constexpr (kSel<M>) {
       s.hi = 0;
       sel_begin(s, s.dpos + 1u, (uint32_t)JG_SEL_STRING);
     }
   } else if (c == '{' || c == '[') {
     const uint32_t arr = c == '[';
-    if constexpr (M >= kSelect) sel_begin(s, s.dpos, arr ? (uint32_t)JG_SEL_ARRAY : (uint32_t)JG_SEL_OBJECT);
+    if constexpr (kSel<M>) sel_begin(s, s.dpos, arr ? (uint32_t)JG_SEL_ARRAY : (uint32_t)JG_SEL_OBJECT);
     if (arr && f == F_AUD) {
       s.aud_arr = 1;
-      if constexpr (M >= kExtract) {
+      if constexpr (kRec<M>) {
         s.aud_off = s.dpos;
         s.present |= 1u << F_AUD;
       }
@@ -516,13 +629,13 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E) {
   } else if (c == 't' || c == 'f' || c == 'n') {
     // null: skipped for iss/sub/jti, absent for a date; any literal elsewhere
     if ((f != F_NONE || elem) && !(c == 'n' && (is_str3 || is_date))) s.bad = 1;
-    if constexpr (M >= kSelect)
+    if constexpr (kSel<M>)
       sel_begin(s, s.dpos, c == 't' ? (uint32_t)JG_SEL_TRUE : c == 'f' ? (uint32_t)JG_SEL_FALSE : (uint32_t)JG_SEL_NULL);
     s.lit = c == 't' ? 0x657572u : c == 'f' ? 0x65736c61u : 0x6c6c75u;   // "rue" / "alse" / "ull"
     s.st = ST_LIT;
   } else if (c == '-' || is_digit(c)) {
     if (!is_date && (f != F_NONE || elem)) s.bad = 1;
-    if constexpr (M >= kSelect) sel_begin(s, s.dpos, (uint32_t)JG_SEL_NUMBER);
+    if constexpr (kSel<M>) sel_begin(s, s.dpos, (uint32_t)JG_SEL_NUMBER);
     s.isdate = is_date;
     s.nlen = 1;
     s.neg = c == '-';
@@ -546,17 +659,18 @@ JG_CL_HD void end_number(ScanT<M>& s) {
     s.exp = s.field == F_EXP ? v : s.exp;
     s.nbf = s.field == F_NBF ? v : s.nbf;
     s.iat = s.field == F_IAT ? v : s.iat;
-    if constexpr (M >= kExtract) s.present |= 1u << s.field;
+    if constexpr (kRec<M>) s.present |= 1u << s.field;
   }
-  if constexpr (M >= kSelect) sel_end(s, s.dpos, 0u);              // dpos: the byte after the literal
+  if constexpr (kSel<M>) sel_end(s, s.dpos, 0u);                   // dpos: the byte after the literal
   // this byte may go on to close the object around the number, itself selected by a shorter path
   if constexpr (M == kPath) sel_commit(s);
   s.st = ST_AFTER;
 }
 
 template <int M, class EX, class SL>
-JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
+JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Preds* Q = nullptr) {
   (void)S;
+  (void)Q;
   if (s.st >= ST_NUM_MINUS && s.st <= ST_NUM_FRAC) {
     const uint32_t d = is_digit(c);
     uint32_t nx = ST_AFTER;                           // ST_AFTER: the number ends here
@@ -598,24 +712,30 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
               s.ksel = slot;
             }
           }
-          if constexpr (M == kPath) {
+          if constexpr (kWalk<M>) {
             // The survivors of this length are this key.  The path that ends here selects the
             // member (equal paths are refused: at most one); a longer one descends if the value is
             // an object, and its slot is ABSENT from here on: this member replaces an earlier one.
             const uint32_t d = s.depth;
-            uint32_t m = s.kcand, slot = 0, desc = 0;
+            uint32_t m = s.kcand, slot = 0, desc = 0, through = 0;
             while (m) {
               const uint32_t b = (uint32_t)__builtin_ctz(m), k = b >> 1;
               m &= m - 1u;
               const bool is = S->len[k][d - 1u] == s.klen, last = S->ncomp[k] == d;
               slot = is && last ? k + 1u : slot;
               desc |= is && !last ? 1u << b : 0u;
+              if constexpr (M == kMatch) through |= is ? Q->all[k] : 0u;
             }
+            (void)through;
             s.desc = desc;
             if (d - 1u < 4u) s.kselv = (s.kselv & ~(0xfu << (4u * (d - 1u)))) | (slot << (4u * (d - 1u)));
-            s.bv = desc;                                        // sel_commit: ABSENT, as a value of type 0 at 0
-            s.voff = 0;
-            s.vtype = 0;
+            if constexpr (M == kPath) {
+              s.bv = desc;                                      // sel_commit: ABSENT, as a value of type 0 at 0
+              s.voff = 0;
+              s.vtype = 0;
+            }
+            // a match scan: the same member takes back what an earlier one of that key gave every path through it
+            if constexpr (M == kMatch) s.res &= ~through;
           }
         } else {
           uint32_t m = s.cand, hit = 0;
@@ -626,19 +746,29 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
           }
           if (s.cmpf == F_AUD) s.aud_found |= hit;
           else if (s.cmpf != F_NONE) s.str_ok |= hit << s.cmpf;
-          if constexpr (M >= kExtract) {
+          if constexpr (kRec<M>) {
             s.iss_len = s.cmpf == F_ISS ? s.pos : s.iss_len;
             s.sub_len = s.cmpf == F_SUB ? s.pos : s.sub_len;
             s.jti_len = s.cmpf == F_JTI ? s.pos : s.jti_len;
             s.aud_len = s.cmpf == F_AUD && !s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud as one string
           }
-          if constexpr (M >= kSelect) sel_end(s, s.dpos, s.hi);
+          if constexpr (kSel<M>) sel_end(s, s.dpos, s.hi);
+          if constexpr (M == kMatch) {                          // the survivors of this length are the string, or its last word
+            uint32_t mm = s.mcand;
+            while (mm) {
+              const uint32_t k = (uint32_t)__builtin_ctz(mm);
+              mm &= mm - 1u;
+              s.res |= Q->len[k] == ((s.mword >> k) & 1u ? s.wpos : s.pos) ? 1u << k : 0u;
+            }
+            s.mcand = 0;
+            s.mword = 0;
+          }
           end_value(s);
         }
       } else {
         if (c < 0x20u || c == '\\') s.bad = 1;
         if (c >= 0x80u && s.ascii_only) s.bad = 1;
-        if constexpr (M >= kSelect) s.hi |= c >= 0x80u;
+        if constexpr (kSel<M>) s.hi |= c >= 0x80u;
         if (s.is_key) {
           if constexpr (M == kSelect) {                         // names still equal to the key so far
             uint32_t m = s.kcand;
@@ -648,7 +778,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
               if (!(s.klen < S->len[k] && S->bytes[S->off[k] + s.klen] == c)) s.kcand &= ~(1u << k);
             }
           }
-          if constexpr (M == kPath) {                           // paths whose component at this depth still equals the key so far
+          if constexpr (kWalk<M>) {                             // paths whose component at this depth still equals the key so far
             uint32_t m = s.kcand;
             while (m) {
               const uint32_t b = (uint32_t)__builtin_ctz(m), k = b >> 1;
@@ -659,6 +789,21 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
           }
           if (s.klen < 3u) s.kw = (s.kw << 8) | (c - 0x61u < 26u ? c - 0x20u : c);
           ++s.klen;
+        }
+        if constexpr (M == kMatch) {
+          // Predicates whose value still equals the string (at pos) or its current word (at wpos).  A
+          // space ends a word -- the word candidates of its length hold -- and arms them all again.
+          const uint32_t sp = c == 0x20u ? s.mword : 0u;
+          uint32_t mm = s.mcand;
+          while (mm) {
+            const uint32_t k = (uint32_t)__builtin_ctz(mm);
+            mm &= mm - 1u;
+            const uint32_t at = (s.mword >> k) & 1u ? s.wpos : s.pos, l = Q->len[k];
+            s.res |= l == at ? sp & (1u << k) : 0u;
+            if (!(at < l && Q->pool[Q->off[k] + at] == c)) s.mcand &= ~(1u << k);
+          }
+          s.mcand |= sp;
+          s.wpos = sp ? 0u : s.wpos + 1u;
         }
         uint32_t m = s.cand;
         while (m) {
@@ -673,7 +818,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
       if (c != (s.lit & 0xffu)) s.bad = 1;
       s.lit >>= 8;
       if (s.lit == 0) {
-        if constexpr (M >= kSelect) sel_end(s, s.dpos + 1u, 0u);
+        if constexpr (kSel<M>) sel_end(s, s.dpos + 1u, 0u);
         end_value(s);
       }
       break;
@@ -682,11 +827,11 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
       else if (!is_ws(c)) s.bad = 1;                   // null, an array, a scalar: the host's business
       break;
     case ST_VALUE:
-      if (!is_ws(c)) begin_value(s, c, E);
+      if (!is_ws(c)) begin_value(s, c, E, Q);
       break;
     case ST_ARR_FIRST:
       if (c == ']') pop(s, 0u);
-      else if (!is_ws(c)) begin_value(s, c, E);
+      else if (!is_ws(c)) begin_value(s, c, E, Q);
       break;
     case ST_OBJ_FIRST:
     case ST_OBJ_KEY:
@@ -698,7 +843,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S) {
         s.kw = 0;
         s.cand = 0;
         if constexpr (M == kSelect) s.kcand = s.depth == 1u ? (1u << S->n) - 1u : 0u;
-        if constexpr (M == kPath) {                      // the paths that are matched down to the object this key is in
+        if constexpr (kWalk<M>) {                        // the paths that are matched down to the object this key is in
           const uint32_t x = s.md ^ ((s.depth - 1u) * 0x5555u);
           s.kcand = s.depth - 1u < 4u ? ~(x | (x >> 1)) & S->ge[s.depth - 1u] : 0u;
         }
@@ -765,9 +910,10 @@ JG_CL_HD uint8_t verdict(const ScanT<M>& s, const EX& E) {
 // verdict-only kernel a third of its registers again).
 template <int M, class Src, class EX, class SL = Select>
 JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* out, const SL* S = nullptr,
-                              jg_selected* sel = nullptr) {
-  if constexpr (M >= kExtract) *out = jg_claims{};                 // JG_CL_HOST: every byte zero
-  if constexpr (M >= kSelect) *sel = jg_selected{};
+                              jg_selected* sel = nullptr, const Preds* Q = nullptr, uint32_t* match = nullptr) {
+  if constexpr (M == kMatch) *match = 0;                           // JG_CL_HOST: no bit
+  if constexpr (kRec<M>) *out = jg_claims{};                       // JG_CL_HOST: every byte zero
+  if constexpr (kSel<M>) *sel = jg_selected{};
   if ((len & 3u) == 1u) return JG_CL_HOST;
   ScanT<M> s;
   const uint32_t groups = (len + 3u) >> 2;
@@ -782,14 +928,14 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
     // Go's strict decoding: the bits the last group does not use are zero
     if (nb < 3u && (trip & (nb == 1u ? 0xffffu : 0xffu))) return JG_CL_HOST;
     for (uint32_t k = 0; k < nb; ++k) {
-      if constexpr (M >= kExtract) s.dpos = 3u * g + k;
-      step(s, (trip >> 16) & 0xffu, E, S);
-      if constexpr (M >= kSelect) sel_commit(s);
+      if constexpr (kRec<M>) s.dpos = 3u * g + k;
+      step(s, (trip >> 16) & 0xffu, E, S, Q);
+      if constexpr (kSel<M>) sel_commit(s);
       trip <<= 8;
     }
   }
   if (s.bad || s.st != ST_DONE) return JG_CL_HOST;
-  if constexpr (M >= kExtract) {
+  if constexpr (kRec<M>) {
     out->exp = s.exp;
     out->nbf = s.nbf;
     out->iat = s.iat;
@@ -804,13 +950,14 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
     out->aud_n = s.aud_n;
     out->present = s.present;
   }
-  if constexpr (M >= kSelect) {
+  if constexpr (kSel<M>) {
     for (uint32_t k = 0; k < JG_MAX_SELECT; ++k) {
       sel->off[k] = s.soff[k];
       sel->len[k] = s.slen[k];
       sel->type[k] = (uint8_t)((s.stype >> (4u * k)) & 0xfu);
     }
   }
+  if constexpr (M == kMatch) *match = s.res;
   return verdict(s, E);
 }
 
@@ -872,6 +1019,17 @@ JG_CL_HD uint8_t claims_paths_each(Src& src, uint32_t len, const Profiles& T, ui
   return scan_segment<kPath>(src, len, E, out, &P, sel);
 }
 
+// claims_decide_each's code for the same input, always, and the predicates that
+// hold (include/jg.h jg_claims_match): bit k of *match is set when predicate k
+// of Q holds on the value claims_paths_each's walk reaches along its path.
+// Filled for every code other than JG_CL_HOST, 0 for JG_CL_HOST.
+template <class Src>
+JG_CL_HD uint8_t claims_match_each(Src& src, uint32_t len, const Profiles& T, uint32_t p, const Paths& P,
+                                   const Preds& Q, uint32_t* match) {
+  const ProfileRef E{T, p};
+  return scan_segment<kMatch>(src, len, E, nullptr, &P, nullptr, &Q, match);
+}
+
 }  // namespace jgclaims
 
 #if defined(__HIPCC__)
@@ -883,6 +1041,7 @@ JG_CL_HD uint8_t claims_paths_each(Src& src, uint32_t len, const Profiles& T, ui
 //   neither select nor paths: vals_out ? k_claims_extract[_each] : k_claims_scan[_each]
 //   select, sel_out  k_claims_select[_each]: and sel_out[i] = the members `select` names (with vals_out)
 //   paths, sel_out   k_claims_paths_each: `paths` in the place of the names (with table and vals_out)
+//   paths, preds, match_out   k_claims_match_each: match_out[i] = the predicates that hold (with table; no record)
 struct ClaimsLaunch {
   const uint8_t* arena = nullptr;
   const jg_cjob* jobs = nullptr;
@@ -891,9 +1050,11 @@ struct ClaimsLaunch {
   const jgclaims::Profiles* table = nullptr;
   const jgclaims::Select* select = nullptr;
   const jgclaims::Paths* paths = nullptr;
+  const jgclaims::Preds* preds = nullptr;
   uint8_t* code_out = nullptr;
   jg_claims* vals_out = nullptr;
   jg_selected* sel_out = nullptr;
+  uint32_t* match_out = nullptr;
 };
 void launch_claims(const ClaimsLaunch& c, hipStream_t s);
 #endif

@@ -17,6 +17,8 @@ returns become `(value, err)` tuples with `err` a str or None.
                                                      token, registered claims scanned on the GPU, no claims map
     (verdict + named claims)                         Validator.RegisteredBatch / SelectBatch (+ Blob forms):
                                                      jwt.Claims and caller-named claims from the same scan
+    (verdict + yes/no questions)                     Validator.MatchBatch / MatchBlob with Equals, HasWord,
+                                                     HasElement, Present: a mask per token from the same scan
     jwt.Expected             jwt/jwt.go:38           Expected
     jwt.SupportedSigningAlgorithm jwt/algs.go:38     SupportedSigningAlgorithm
 
@@ -181,6 +183,53 @@ def _paths_of(names):
     if not any(isinstance(x, Path) for x in names):
         return names, None
     return names, [list(x) if isinstance(x, Path) else [x] for x in names]
+
+
+class Require(tuple):
+    """A yes/no question about one claim, an element of the `requires` of
+    MatchBatch / MatchBlob and their *Each forms: (path, op, value).  Built by
+    Equals, HasWord, HasElement and Present."""
+    EQUALS, HAS_WORD, HAS_ELEMENT, PRESENT = 1, 2, 3, 4          # jg_pred_op (include/jg.h)
+
+    def __new__(cls, path_or_name, op, value=""):
+        path = path_or_name if isinstance(path_or_name, Path) else Path(path_or_name)
+        if not isinstance(value, str):
+            raise TypeError("Require: the value is a str")
+        return super().__new__(cls, (path, int(op), value))
+
+    def __repr__(self):
+        name = {1: "Equals", 2: "HasWord", 3: "HasElement", 4: "Present"}.get(self[1], "Require")
+        return "%s(%r%s)" % (name, self[0], "" if self[1] == self.PRESENT else ", %r" % self[2])
+
+
+def Equals(path_or_name, v: str) -> Require:
+    """The claim is a string equal to v ("" allowed)."""
+    return Require(path_or_name, Require.EQUALS, v)
+
+
+def HasWord(path_or_name, v: str) -> Require:
+    """The claim is a string and one of its space-separated words (Go's
+    strings.Split(s, " "), the RFC 6749 scope form) equals v."""
+    return Require(path_or_name, Require.HAS_WORD, v)
+
+
+def HasElement(path_or_name, v: str) -> Require:
+    """The claim is an array and one of its direct elements is a string equal to v."""
+    return Require(path_or_name, Require.HAS_ELEMENT, v)
+
+
+def Present(path_or_name) -> Require:
+    """The claims map holds the claim; null counts."""
+    return Require(path_or_name, Require.PRESENT, "")
+
+
+def _requires_of(requires):
+    out = []
+    for r in requires:
+        if not isinstance(r, Require):
+            raise TypeError("requires: elements are built by Equals, HasWord, HasElement or Present")
+        out.append((list(r[0]), r[1], r[2]))
+    return out
 
 
 class Validator:
@@ -367,6 +416,53 @@ class Validator:
             stats.update(scanned=scanned, host=host)
         return cols
 
+    # ---- yes/no questions about claims, answered by the GPU scan where the bytes are
+    def MatchBatch(self, tokens: Sequence, requires: Sequence[Require], expected: Expected = None,
+                   stats: dict = None):
+        """CheckBatch plus requirements on claims: [(bits or None, err or None)], err ==
+        Validate(tokens[i], expected)[1]; for an accepted token bit k of bits says
+        whether requires[k] (Equals / HasWord / HasElement / Present, on a name or a
+        Path) holds on ValidateBatch's claims map for it; a rejected token carries
+        None.  A requirement never changes err.  The scan compares the values while
+        it walks the payload and returns four bytes per token: no claims map, no
+        text, no column.  A list the scan does not take (more than 8 distinct paths,
+        a path over 4 components, a value over 64 bytes or not printable ASCII
+        without quote and backslash, an empty value or one with a space for HasWord,
+        an empty value for HasElement) still answers, from the host path.  More than
+        16 requirements, or a NUL in a component or a value, raise ValueError.
+        `stats` as in CheckBatch."""
+        rows, scanned, host = self._impl.match_batch(list(tokens), _requires_of(requires),
+                                                     (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return [tuple(r) for r in rows]
+
+    def MatchBlob(self, blob: bytes, requires: Sequence[Require], expected: Expected = None,
+                  stats: dict = None) -> dict:
+        """MatchBatch's throughput form: newline-separated tokens -> {"ok": n accept
+        bytes, "match": n little-endian uint32 masks (0 for a rejected token)}."""
+        cols, scanned, host = self._impl.match_blob(blob, _requires_of(requires), (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
+    def MatchBatchEach(self, tokens: Sequence, requires: Sequence[Require], expected: Sequence[Expected],
+                       which: Sequence[int], stats: dict = None):
+        """MatchBatch with expected[which[i]] for tokens[i]; one requirement list for the batch."""
+        rows, scanned, host = self._impl.match_batch_each(list(tokens), _requires_of(requires),
+                                                          self._natives(expected), list(which))
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return [tuple(r) for r in rows]
+
+    def MatchBlobEach(self, blob: bytes, requires: Sequence[Require], expected: Sequence[Expected], which,
+                      stats: dict = None) -> dict:
+        """MatchBlob with expected[which[i]] for token i; `which` as in CheckBlobEach."""
+        cols, scanned, host = self._impl.match_blob_each(blob, _requires_of(requires), self._natives(expected), which)
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
 
 def NewValidator(keyset: Optional[KeySet]):
     if keyset is None:
@@ -377,4 +473,4 @@ def NewValidator(keyset: Optional[KeySet]):
 __all__ = ["RS256", "RS384", "RS512", "ES256", "ES384", "ES512", "PS256", "PS384", "PS512", "EdDSA",
            "DefaultLeewaySeconds", "PublicKey", "SupportedSigningAlgorithm", "ParsePublicKeyPEM", "KeySet",
            "NewStaticKeySet", "NewJSONWebKeySet", "NewOIDCDiscoveryKeySet", "Expected", "Path", "Validator",
-           "NewValidator"]
+           "NewValidator", "Require", "Equals", "HasWord", "HasElement", "Present"]

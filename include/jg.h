@@ -564,6 +564,64 @@ int jg_claims_paths(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                     const jg_expect* expects, uint32_t nexpect, const jg_paths* paths,
                     uint8_t* code_out, jg_claims* vals_out, jg_selected* sel_out);
 
+/* ---- the scan that answers yes/no questions about claims ----
+ * jg_claims_paths for callers that read a claim only to test it (does scope
+ * hold orders:read, is admin among realm_access.roles, is azp this client, is
+ * cnf.jkt there): the same jobs, profiles and `paths`, and instead of records
+ * one mask per token.  `preds` holds up to JG_MAX_PRED predicates, each a path
+ * (an index into `paths`; several predicates may name one path), an operator
+ * and a value (the values back to back in `values`).  Bit k of match_out[i] is
+ * set exactly when predicate k holds on the claims map the host builds for that
+ * payload.  With v the value jg_claims_paths' walk reaches along paths[path[k]]
+ * (objects only, never arrays; the last member of a key wins; a repeated parent
+ * replaces the earlier one wholesale):
+ *  - JG_PRED_EQUALS: v is a string whose bytes equal the value.  value_len 0
+ *    is allowed and means "";
+ *  - JG_PRED_HAS_WORD: v is a string and one of the pieces of
+ *    strings.Split(v, " ") equals the value (only 0x20 separates; the RFC 6749
+ *    scope form).  The value is 1..JG_PRED_VALUE_MAX bytes without a space;
+ *  - JG_PRED_HAS_ELEMENT: v is an array and one of its direct elements is a
+ *    string equal to the value (1..JG_PRED_VALUE_MAX bytes).  Other elements
+ *    never match, nested arrays and objects are not searched, a string v does
+ *    not match;
+ *  - JG_PRED_PRESENT: the walk reaches a value; null counts.  value_len is 0.
+ * Value bytes are 0x20..0x7e without " and \ (a name's bytes under jg_select's
+ * rules).  A string that holds bytes >= 0x80 is compared as its raw bytes, so it
+ * never equals an ASCII value, and its other words still count.  That is exact
+ * against Go: the decoder replaces invalid UTF-8 with U+FFFD, which is three
+ * bytes >= 0x80 -- never a space, never an ASCII byte -- and leaves every byte
+ * < 0x80 where it is, so the ASCII runs of the Go string and of the raw bytes,
+ * and the places where 0x20 splits them, are the same (a string with a
+ * backslash is JG_CL_HOST already).
+ * code_out[i] is jg_claims_each's code for the same jobs and profiles, byte for
+ * byte, always: predicates never change a decision and no payload is
+ * JG_CL_HOST because of them.  For JG_CL_HOST match_out[i] is 0; for every
+ * other code, failure codes included, it is filled.  Bits n..31 are 0; with
+ * preds->n == 0 every mask is 0.
+ * jobs[i].flags is the profile index.  Everything else is jg_claims_paths':
+ * blocking, first device, the scan's stream and lock, kept buffers (two more:
+ * the resolved predicates, uploaded whole per call, and the masks), -2 on an
+ * infrastructure error or an unusable context, njobs == 0 returns 0 without
+ * touching the buffers.  -1: everything jg_claims_paths refuses; preds->n over
+ * JG_MAX_PRED; a path[k] >= paths->n; an unknown op; a value_len outside the
+ * op's range; a refused value byte; a space in a HAS_WORD value; two identical
+ * predicates (same path, op and value); paths, preds, code_out or match_out
+ * NULL with njobs > 0. */
+#define JG_MAX_PRED 16
+#define JG_PRED_VALUE_MAX 64
+enum jg_pred_op { JG_PRED_EQUALS = 1, JG_PRED_HAS_WORD = 2, JG_PRED_HAS_ELEMENT = 3, JG_PRED_PRESENT = 4 };
+typedef struct jg_preds {
+  const uint8_t* values;                     /* the predicates' values, back to back */
+  uint32_t n;                                /* 0..JG_MAX_PRED */
+  uint8_t  path[JG_MAX_PRED];                /* index into the call's jg_paths */
+  uint8_t  op[JG_MAX_PRED];                  /* jg_pred_op */
+  uint32_t value_len[JG_MAX_PRED];
+} jg_preds;
+int jg_claims_match(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                    const jg_cjob* jobs, size_t njobs,
+                    const jg_expect* expects, uint32_t nexpect, const jg_paths* paths, const jg_preds* preds,
+                    uint8_t* code_out, uint32_t* match_out);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 
