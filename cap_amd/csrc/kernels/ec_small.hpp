@@ -365,7 +365,9 @@ __global__ void __launch_bounds__(SM_THREADS) k_ec_small(EcSmallArgs a) {
       for (int j = 0; j < L; ++j) { u1[j] = sc[L + j]; u2[j] = sc[2 * L + j]; }
       ok = ec_exact_ok<CV>(a.keyblob + K.aux_off, r, u1, u2);
     } else if (!P.inf) {                          // R = infinity: rejected
-      ok = ec_x_matches<CV>(P.X, P.Z, r);
+      uint32_t zz[L];
+      mp::sqr<Fp>(zz, P.Z);
+      ok = ec_x_matches<CV>(P.X, zz, r);
     }
   }
   a.verdict[a.out[blockIdx.x]] = ok ? 1 : 0;

@@ -46,6 +46,12 @@ enum : int32_t { EC_ALL = 0, EC_FAST = 1, EC_EXACT = 2 };
 #endif
 // The curves whose k_ec_point loops and takes the cap: ec_point_persistent
 // (point_form.hpp).  grp_next and point_blocks are not read for the others.
+// The curves whose k_ec_point carries the accumulator as (X, Y, ZZ, ZZZ)
+// instead of Jacobian (X, Y, Z): one squaring and one reduction less per mixed
+// addition and in the accept test, for one more coordinate in registers
+// (ecdsa_impl.hpp madd_xyzz).  P-256; DESIGN.md section 5 has the other curves.
+// The split, prefetch and small forms stay Jacobian on every curve.
+constexpr bool ec_point_xyzz(int cls) { return cls == PF_CLS_P256; }
 static_assert(PF_CLS_P256 == jgk::CLS_P256 && PF_CLS_P384 == jgk::CLS_P384 && PF_CLS_P521 == jgk::CLS_P521 &&
               PF_CLS_ED25519 == jgk::CLS_ED25519, "point_form.hpp numbers the classes as common.hpp does");
 

@@ -12,7 +12,8 @@
 //   k_ec_point  : R = u1 G + u2 Q as a sum of one precomputed affine multiple of
 //                 G and one of Q per window (comb tables in HBM: entries
 //                 d * 2^(W w) * P, d = 1..2^(W-1)), mixed Jacobian+affine
-//                 additions, no doublings; accept iff X == r Z^2 or (r+n) Z^2
+//                 additions (P-256: XYZZ+affine, ec_point_xyzz), no doublings;
+//                 accept iff X == r Z^2 or (r+n) Z^2
 //   k_ec_exact  : tokens whose fast sum hit an exceptional case of the group
 //                 law (Z == 0: a doubling, an inverse pair, or R = infinity) --
 //                 recomputed with complete case handling; rare
@@ -441,6 +442,68 @@ __device__ __forceinline__ void madd_z1(uint32_t* X, uint32_t* Y, uint32_t* Z, c
   y3_from<Fp>(Y, r, t, y1, hhh);
 }
 
+// Mixed addition on the XYZZ accumulator (x = X/ZZ, y = Y/ZZZ, ZZ^3 == ZZZ^2;
+// EFD madd-2008-s): P1 (X < 10m on KX3 fields, else < 2m; Y, ZZ, ZZZ < 2m;
+// 28-bit limbs) += P2 (affine x2, y2).  8M + 2S under 9 reductions: Z is used
+// by madd only to rebuild Z^2 and Z^3, which are carried here instead, and the
+// accept test needs Z^2 alone (ec_x_matches).
+// Operand bounds of the four products madd does not have (mp.hpp: limbs
+// < 3*2^28, value(a) value(b) < R m); none is wider than a pair madd multiplies:
+//   x2 ZZ    : canonical entry (28-bit limbs, < m) x normalized (< 2m) -- madd's
+//              x2 z1z1 has the semi-normalized z1z1 (limbs < 2^32) here
+//   y2 ZZZ   : y2 negated has limbs < 2^29 + 2^28, value <= 4m; x normalized,
+//              as madd's y2 t
+//   ZZ hh, ZZZ hhh : two reduction outputs each (28-bit limbs, < 2m), as t = Z z1z1
+// h, r, hh, hhh, v and the products x3_from / y3_from take are madd's own.
+// ZZ3 before v, ZZZ3 right after hhh: X dies at v, h and hh at hhh.
+// An exceptional pair (P1 == +-P2) yields h == 0 and so ZZ3 == ZZZ3 == 0, which
+// is absorbing in later additions (u2 == s2 == 0, ZZ3 = 0 hh) and is detected
+// at the end.
+template <class Fp>
+__device__ __forceinline__ void madd_xyzz(uint32_t* X, uint32_t* Y, uint32_t* ZZ, uint32_t* ZZZ, const uint32_t* x2,
+                                          const uint32_t* y2) {
+  constexpr int L = Fp::L;
+  uint32_t u2[L], s2[L], h[L], r[L], hh[L], hhh[L], v[L], t[L];
+  mp::mulf<Fp>(u2, x2, ZZ);
+  mp::mulf<Fp>(s2, y2, ZZZ);
+  sub_x<Fp>(h, u2, X);
+  mp::sub<Fp>(r, s2, Y);
+  mp::norm_for_mulf<Fp>(h);                  // P-384: h, r are squared (mulf precondition)
+  mp::norm_for_mulf<Fp>(r);
+  mp::sqrf<Fp>(hh, h);
+  mp::mulf<Fp>(ZZ, ZZ, hh);
+  mp::mulf<Fp>(v, X, hh);
+  mp::mulf<Fp>(hhh, h, hh);
+  mp::mulf<Fp>(ZZZ, ZZZ, hhh);
+  uint32_t y1[L];
+  mp::copy<Fp>(y1, Y);
+  x3_from<Fp>(X, r, hhh, v);
+  // Y3 = r (v - X3) - Y1 hhh
+  sub_x<Fp>(t, v, X);
+  y3_from<Fp>(Y, r, t, y1, hhh);
+}
+
+// madd_xyzz with ZZ1 == ZZZ1 == 1 (the accumulator after its first
+// assignment): u2 = x2, s2 = y2, ZZ3 = hh and ZZZ3 = hhh are copies of two
+// reduction outputs -- 4M + 2S, as madd_z1.
+template <class Fp>
+__device__ __forceinline__ void madd_xyzz_z1(uint32_t* X, uint32_t* Y, uint32_t* ZZ, uint32_t* ZZZ, const uint32_t* x2,
+                                             const uint32_t* y2) {
+  constexpr int L = Fp::L;
+  uint32_t h[L], r[L], v[L], t[L], y1[L];
+  mp::sub<Fp>(h, x2, X);
+  mp::sub<Fp>(r, y2, Y);
+  mp::norm<Fp>(h);                           // 28-bit limbs, value < 6m, as madd_z1
+  mp::norm<Fp>(r);                           // y2 may be negated (limbs < 2^29): keep r^2's columns in range
+  mp::sqrf<Fp>(ZZ, h);
+  mp::mulf<Fp>(ZZZ, h, ZZ);
+  mp::mulf<Fp>(v, X, ZZ);
+  mp::copy<Fp>(y1, Y);
+  x3_from<Fp>(X, r, ZZZ, v);
+  sub_x<Fp>(t, v, X);
+  y3_from<Fp>(Y, r, t, y1, ZZZ);
+}
+
 // A table entry (affine x, y; canonical Montgomery form): 2L limbs, or 16
 // packed words for P-256 (ecdsa.hpp ec_packed)
 template <class CV>
@@ -497,8 +560,11 @@ __device__ __forceinline__ void load_ent(RawEnt<CV>& r, const uint32_t* __restri
 }
 // The accumulator += the entry r for digit d (nothing for d == 0).
 // Z1ONE: the accumulator, if not empty, holds exactly one table entry (Z == 1)
-template <class CV, bool Z1ONE = false>
-__device__ __forceinline__ void add_ent(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty, const RawEnt<CV>& r, int d) {
+// XYZZ: the accumulator is (X, Y, ZZ, ZZZ) -- Z holds ZZ -- instead of Jacobian
+// (X, Y, Z), which leaves ZZZ unused
+template <class CV, bool Z1ONE = false, bool XYZZ = false>
+__device__ __forceinline__ void add_ent(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty, const RawEnt<CV>& r, int d,
+                                        uint32_t* ZZZ = nullptr) {
   using Fp = typename CV::Fp;
   constexpr int L = Fp::L;
   if (d == 0) return;
@@ -515,7 +581,11 @@ __device__ __forceinline__ void add_ent(uint32_t* X, uint32_t* Y, uint32_t* Z, b
     mp::copy<Fp>(X, x2);
     mp::copy<Fp>(Y, y2); mp::freduce<Fp>(Y);
     mp::set_const<Fp>(Z, Fp::ONE);
+    if constexpr (XYZZ) mp::set_const<Fp>(ZZZ, Fp::ONE);
     empty = false;
+  } else if constexpr (XYZZ) {
+    if constexpr (Z1ONE) madd_xyzz_z1<Fp>(X, Y, Z, ZZZ, x2, y2);
+    else madd_xyzz<Fp>(X, Y, Z, ZZZ, x2, y2);
   } else if constexpr (Z1ONE) {
     madd_z1<Fp>(X, Y, Z, x2, y2);
   } else {
@@ -524,15 +594,15 @@ __device__ __forceinline__ void add_ent(uint32_t* X, uint32_t* Y, uint32_t* Z, b
 }
 
 // entry |d| of window w of a comb table, loaded and added
-template <class CV, bool GEN, bool Z1ONE = false>
+template <class CV, bool GEN, bool Z1ONE = false, bool XYZZ = false>
 __device__ __forceinline__ void add_window(uint32_t* X, uint32_t* Y, uint32_t* Z, bool& empty,
-                                           const uint32_t* __restrict__ tab, int w, int d) {
+                                           const uint32_t* __restrict__ tab, int w, int d, uint32_t* ZZZ = nullptr) {
   constexpr int STRIDE = ec_stride(CV::CLS), NE = GEN ? ec_entries(CV::CLS, true) : 1 << (CV::WQ - 1);
   if (d == 0) return;
   const int ad = d < 0 ? -d : d;
   RawEnt<CV> r;
   load_ent<CV>(r, tab + ((int64_t)w * NE + (ad - 1)) * STRIDE);
-  add_ent<CV, Z1ONE>(X, Y, Z, empty, r, d);
+  add_ent<CV, Z1ONE, XYZZ>(X, Y, Z, empty, r, d, ZZZ);
 }
 
 // r of token p as plain limbs, from the signature rows
@@ -545,15 +615,15 @@ __device__ __forceinline__ void ec_load_r(const EcArgs& a, int64_t p, uint32_t* 
   mp::words_to_limbs<CV::Fp::L, CW>(r, rw);
 }
 
-// x(R) mod n == r for R = (X : Y : Z) Jacobian, Z != 0:
-// X == r Z^2, or r + n < p and X == (r + n) Z^2
+// x(R) mod n == r for R with x = X / zz, zz != 0 (normalized: the XYZZ
+// accumulator's ZZ, or a Jacobian caller's own Z^2):
+// X == r zz, or r + n < p and X == (r + n) zz
 template <class CV>
-__device__ __forceinline__ bool ec_x_matches(const uint32_t* X, const uint32_t* Z, const uint32_t* r) {
+__device__ __forceinline__ bool ec_x_matches(const uint32_t* X, const uint32_t* zz, const uint32_t* r) {
   using Fp = typename CV::Fp;
   using Fn = typename CV::Fn;
   constexpr int L = Fp::L;
-  uint32_t zz[L], rm[L], tt[L];
-  mp::sqr<Fp>(zz, Z);
+  uint32_t rm[L], tt[L];
   mp::to_mont<Fp>(rm, r);
   mp::mul<Fp>(tt, rm, zz);
   bool ok = mp::eq_mod<Fp>(X, tt);
@@ -586,20 +656,24 @@ __device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p)
   const uint32_t* __restrict__ qtab = key_table(a.keys[kidx]);
   const uint32_t* __restrict__ gtab = a.gtab;
 
-  uint32_t X[L], Y[L], Z[L];
+  // the accumulator: (X, Y, ZZ, ZZZ) on the curves of ec_point_xyzz (Z holds
+  // ZZ), else Jacobian (X, Y, Z)
+  constexpr bool XYZZ = ec_point_xyzz(CV::CLS);
+  uint32_t X[L], Y[L], Z[L], ZZZ[XYZZ ? L : 1];
   bool empty = true;
   // window 0 peeled: its G entry is an assignment, so its Q entry adds onto Z == 1
-  add_window<CV, true>(X, Y, Z, empty, gtab, 0, (int)a.digs[p]);
-  add_window<CV, false, true>(X, Y, Z, empty, qtab, 0, (int)a.digs[(int64_t)NG * np + p]);
+  add_window<CV, true, false, XYZZ>(X, Y, Z, empty, gtab, 0, (int)a.digs[p], ZZZ);
+  add_window<CV, false, true, XYZZ>(X, Y, Z, empty, qtab, 0, (int)a.digs[(int64_t)NG * np + p], ZZZ);
   for (int w = 1; w < NWIN; ++w) {
-    if (w < NG) add_window<CV, true>(X, Y, Z, empty, gtab, w, (int)a.digs[(int64_t)w * np + p]);
-    if (w < NQ) add_window<CV, false>(X, Y, Z, empty, qtab, w, (int)a.digs[(int64_t)(NG + w) * np + p]);
+    if (w < NG) add_window<CV, true, false, XYZZ>(X, Y, Z, empty, gtab, w, (int)a.digs[(int64_t)w * np + p], ZZZ);
+    if (w < NQ)
+      add_window<CV, false, false, XYZZ>(X, Y, Z, empty, qtab, w, (int)a.digs[(int64_t)(NG + w) * np + p], ZZZ);
   }
   if (empty) { a.verdict_pad[p] = 0; return; }           // R = infinity (unreachable: u2 != 0)
   uint32_t zc[L];
   mp::copy<Fp>(zc, Z);
   mp::canon<Fp>(zc);
-  if (mp::is_zero_canon<Fp>(zc)) {                        // exceptional case: exact recompute
+  if (mp::is_zero_canon<Fp>(zc)) {                        // exceptional case (Z or ZZ == 0): exact recompute
     const uint32_t idx = atomicAdd(a.exc_count, 1u);
     a.exc_list[idx] = (int32_t)p;
     a.status[p] = ST_EXCEPTIONAL;
@@ -607,7 +681,13 @@ __device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p)
   }
   uint32_t r[L];
   ec_load_r<CV>(a, p, r);
-  a.verdict_pad[p] = ec_x_matches<CV>(X, Z, r);
+  if constexpr (XYZZ) {
+    a.verdict_pad[p] = ec_x_matches<CV>(X, Z, r);
+  } else {
+    uint32_t zz[L];
+    mp::sqr<Fp>(zz, Z);
+    a.verdict_pad[p] = ec_x_matches<CV>(X, zz, r);
+  }
 }
 
 // Persistent: each one-wave block takes 64-token groups of [begin, end) from
@@ -621,8 +701,16 @@ __device__ __forceinline__ void ec_point_token(const EcArgs& a, const int64_t p)
 // kernel's tail.
 // P-256 only (ec_point_persistent): the P-384 kernel measured no gain under
 // the cap, so P-384 and P-521 keep one block per group.
+// JG_EC_POINT_ATTR: per translation unit, as JG_EC_SCALAR_ATTR.  ecdsa_p256.hip
+// holds the kernel at four waves per SIMD: with the XYZZ accumulator's fourth
+// coordinate the scheduler otherwise spends 139 VGPRs (three waves) where 110
+// do, with no scratch.  ecdsa_p384.hip states the same
+// bound for its Jacobian kernel (120 VGPRs).
+#ifndef JG_EC_POINT_ATTR
+#define JG_EC_POINT_ATTR
+#endif
 template <class CV>
-__global__ void __launch_bounds__(64) k_ec_point(EcArgs a) {
+__global__ void __launch_bounds__(64) JG_EC_POINT_ATTR k_ec_point(EcArgs a) {
   if constexpr (!ec_point_persistent(CV::CLS)) {
     ec_point_token<CV>(a, a.begin + (int64_t)blockIdx.x * WAVE + threadIdx.x);
     return;
@@ -904,7 +992,9 @@ __global__ void __launch_bounds__(64) k_ec_point_split(EcArgs a) {
   if (P.inf) { a.verdict_pad[p] = 0; return; }    // R = infinity: rejected
   uint32_t r[L];
   ec_load_r<CV>(a, p, r);
-  a.verdict_pad[p] = ec_x_matches<CV>(P.X, P.Z, r);
+  uint32_t zz[L];
+  mp::sqr<Fp>(zz, P.Z);
+  a.verdict_pad[p] = ec_x_matches<CV>(P.X, zz, r);
 }
 
 // ------------------------------------------------------------------ staging

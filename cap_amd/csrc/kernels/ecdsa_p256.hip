@@ -1,5 +1,7 @@
 // ecdsa_p256.hip -- the P256 instantiations of ecdsa_impl.hpp: the verify
 // chain, key staging and generator table for every key-table width.
+// k_ec_point at four waves per SIMD (ecdsa_impl.hpp JG_EC_POINT_ATTR)
+#define JG_EC_POINT_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 #include "ecdsa_impl.hpp"
 #include "ec_small.hpp"
 

@@ -1,5 +1,10 @@
 // ecdsa_p384.hip -- the P384 instantiations of ecdsa_impl.hpp: the verify
 // chain, key staging and generator table for every key-table width.
+// k_ec_point at four waves per SIMD (ecdsa_impl.hpp JG_EC_POINT_ATTR): 120
+// VGPRs, no scratch.  Unbounded, the allocator's choice sits close to the
+// 128-register step and has gone to 129 (three waves) on an edit elsewhere in
+// the header that leaves this kernel's code alone.
+#define JG_EC_POINT_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 #include "ecdsa_impl.hpp"
 #include "ec_small.hpp"
 
