@@ -28,7 +28,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest", "jg_debug_table_read",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
            "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
-           "jg_claims_paths", "jg_claims_match"]
+           "jg_claims_paths", "jg_claims_match", "jg_claims_match_args"]
 
 
 class JgKey(ctypes.Structure):
@@ -122,12 +122,67 @@ class JgPaths(ctypes.Structure):
 MAX_PRED, PRED_VALUE_MAX = 16, 64            # JG_MAX_PRED, JG_PRED_VALUE_MAX
 # jg_pred_op
 PRED_EQUALS, PRED_HAS_WORD, PRED_HAS_ELEMENT, PRED_PRESENT = 1, 2, 3, 4
+# ... and those only jg_claims_match_args takes: the value is a column index (one byte) or an int64 bound
+PRED_EQUALS_ARG, PRED_NUM_GE, PRED_NUM_LE, PRED_NUM_GE_ARG, PRED_NUM_LE_ARG = 5, 6, 7, 8, 9
+MAX_ARGS = 4                                 # JG_MAX_ARGS
 
 
 class JgPreds(ctypes.Structure):
     """jg_preds: the caller's predicates, their values back to back in `values`"""
     _fields_ = [("values", ctypes.c_void_p), ("n", ctypes.c_uint32), ("path", ctypes.c_uint8 * MAX_PRED),
                 ("op", ctypes.c_uint8 * MAX_PRED), ("value_len", ctypes.c_uint32 * MAX_PRED)]
+
+
+class JgSArg(ctypes.Structure):
+    """jg_sarg: one string operand, a span of jg_args.bytes"""
+    _fields_ = [("off", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+class JgArgs(ctypes.Structure):
+    """jg_args: the per-job operands of jg_claims_match_args"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("bytes_len", ctypes.c_size_t), ("str", ctypes.c_void_p),
+                ("num", ctypes.c_void_p), ("nstr", ctypes.c_uint32), ("nnum", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(JgSArg) == 8
+
+
+def pack_args(strs=(), nums=(), lead=0):
+    """Operand columns -> the dict Context.claims_match_args takes.  `strs`: string
+    columns, each one bytes per job; `nums`: int64 columns, each one int per job.
+    The operands are packed job-major, back to back after `lead` filler bytes, so
+    the last one ends at the last byte.  {"bytes", "spans": a row of (off, len) per
+    job, "nums": a row of ints per job, "nstr", "nnum"}: a test may edit any of it."""
+    n = len(strs[0]) if strs else len(nums[0]) if nums else 0
+    blob, spans = bytearray(b"#" * lead), []
+    for i in range(n):
+        row = []
+        for col in strs:
+            v = bytes(col[i])
+            row.append((len(blob), len(v)))
+            blob += v
+        spans.append(row)
+    return {"bytes": bytes(blob), "spans": spans, "nums": [[int(col[i]) for col in nums] for i in range(n)],
+            "nstr": len(strs), "nnum": len(nums)}
+
+
+def _jg_args(a, null=()):
+    """pack_args' dict -> (JgArgs, the buffers to keep alive)"""
+    blob = a["bytes"]
+    keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+    flat = [x for row in a["spans"] for x in row]
+    sp = (JgSArg * max(1, len(flat)))()
+    for t, (off, ln) in zip(sp, flat):
+        t.off, t.len = off, ln
+    fn = [x for row in a["nums"] for x in row]
+    nm = (ctypes.c_int64 * max(1, len(fn)))(*fn)
+    g = JgArgs()
+    g.bytes = None if "bytes" in null else ctypes.cast(keep, ctypes.c_void_p)
+    g.bytes_len = a.get("bytes_len", len(blob))
+    g.str = None if "str" in null else ctypes.cast(sp, ctypes.c_void_p)
+    g.num = None if "num" in null else ctypes.cast(nm, ctypes.c_void_p)
+    g.nstr, g.nnum = a["nstr"], a["nnum"]
+    return g, (keep, sp, nm)
 
 
 def _cjobs(rows):
@@ -269,6 +324,9 @@ def lib():
                                       ctypes.c_uint32, ctypes.POINTER(JgPaths), vp, vp, vp]
         L.jg_claims_match.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
                                       ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds), vp, vp]
+        L.jg_claims_match_args.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                           ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds),
+                                           ctypes.POINTER(JgArgs), vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -578,6 +636,29 @@ class Context:
                           len(expects) if nexpect is None else nexpect,
                           None if "paths" in null else ctypes.byref(ps),
                           None if "preds" in null else ctypes.byref(qs),
+                          None if "codes" in null else out,
+                          None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
+        return out.raw[:n], list(masks[:n])
+
+    def claims_match_args(self, arena_bytes, jobs, expects, paths, preds, args, nexpect=None, null=()):
+        """jg_claims_match_args: claims_match with the jobs' own operands.  `preds`
+        may hold the ops PRED_EQUALS_ARG, PRED_NUM_GE_ARG and PRED_NUM_LE_ARG (the
+        value is one byte, the column) and PRED_NUM_GE / PRED_NUM_LE (the value is
+        the bound as 8 little-endian bytes); `args`: pack_args' dict -> (codes:
+        bytes, masks: list of int), both poisoned with 0xee before the call.  `null`
+        names arguments ("paths", "preds", "args", "codes", "masks") or members of
+        the operands ("bytes", "str", "num") to pass as NULL."""
+        n = len(jobs)
+        es, _keep = _jg_expects(expects)
+        ps, _nkeep = _jg_paths(paths)
+        qs, _vkeep = _jg_preds(preds)
+        ga, _akeep = _jg_args(args, null)
+        out, masks = _poisoned(ctypes.c_char, n), _poisoned(ctypes.c_uint32, n)
+        self._claims_call("jg_claims_match_args", arena_bytes, _cjobs(jobs), n, es,
+                          len(expects) if nexpect is None else nexpect,
+                          None if "paths" in null else ctypes.byref(ps),
+                          None if "preds" in null else ctypes.byref(qs),
+                          None if "args" in null else ctypes.byref(ga),
                           None if "codes" in null else out,
                           None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
         return out.raw[:n], list(masks[:n])

@@ -2003,6 +2003,21 @@ struct MatchPlan {
   bool usable = true;
   bool identity = true;                              // bit[k] == k for every k: the scan's mask is the caller's
   explicit MatchPlan(const std::vector<Require>& reqs);
+  // The MatchBatchArgs entries: the requirements may take operands, n per column.  The operands travel as a
+  // jg_args (job-major spans into `abytes`, numbers in `anums`); host_only[i]: token i has a string operand the
+  // scan refuses, so it is not scanned and its spans are empty.
+  MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vector<std::vector<std::string_view>>& strs,
+            const std::vector<const int64_t*>& nums, bool with_args = true);
+  bool with_args = false;
+  const std::vector<std::vector<std::string_view>>* strs = nullptr;
+  const std::vector<const int64_t*>* nums = nullptr;
+  std::string abytes;
+  std::vector<jg_sarg> aspans;
+  std::vector<int64_t> anums;
+  std::vector<uint8_t> host_only;
+  jg_args args{};
+  // token i's operands for the host path
+  uint32_t host_bits(const json::Value& claims, size_t i) const;
   // the caller's mask from the scan's
   uint32_t spread(uint32_t m) const {
     if (identity) return m;
@@ -2132,6 +2147,8 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
         j.len = 0;
         j.flags = 0;
         if (!t.ncand || !t.lit) continue;
+        if constexpr (M == kMatchMode)
+          if (match->with_args && match->host_only[i]) continue;   // an operand the scan refuses: the host path
         if constexpr (Each) {
           const int32_t sl = slot[which[i]];
           if (sl < 0) continue;                           // no slot: the host path
@@ -2147,10 +2164,14 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     pt.lap("scan-jobs");
     try {
       const jg_expect& ex = exs[0];
-      if constexpr (M == kMatchMode)
-        eng.claims_match(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths, &match->preds,
-                         code, masks, true);
-      else if constexpr (M == kPathMode)
+      if constexpr (M == kMatchMode) {
+        if (match->with_args)
+          eng.claims_match_args(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
+                                &match->preds, &match->args, code, masks, true);
+        else
+          eng.claims_match(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
+                           &match->preds, code, masks, true);
+      } else if constexpr (M == kPathMode)
         eng.claims_paths(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), paths, code, recs, sels, true);
       else if constexpr (Each)
         eng.claims_each(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(),
@@ -2208,7 +2229,8 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
         } else {
           Result v = validate_claims(r.claims, t.view(), expected, now);
           if constexpr (M == kMatchMode) {
-            const uint32_t bits = v.ok ? match_requires(r.claims, match->reqs) : 0u;
+            const uint32_t bits = !v.ok ? 0u : match->with_args ? match->host_bits(r.claims, i)
+                                                                : match_requires(r.claims, match->reqs);
             put(i, v.ok, std::move(v.err), bits);
           } else {
             put(i, v.ok, std::move(v.err));
@@ -2792,20 +2814,54 @@ void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size
 // ---- MatchBatch: predicates on claims, answered by the scan ----
 namespace {
 // what MatchBatch refuses whatever path decides the tokens
-void check_requires(const std::vector<Require>& reqs) {
+void check_requires(const std::vector<Require>& reqs, bool with_args = false) {
   if (reqs.size() > kMaxRequires) throw std::invalid_argument("capjwt: more than 16 requirements: the mask has no bit for them");
   for (const Require& r : reqs) {
     if (r.path.empty()) throw std::invalid_argument("capjwt: a claim path has no component");
     for (const std::string& comp : r.path)
       if (comp.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim path holds a NUL byte");
     if (r.value.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a required value holds a NUL byte");
-    if (r.op < Require::Equals || r.op > Require::Present) throw std::invalid_argument("capjwt: an unknown requirement op");
+    if (r.op < Require::Equals || r.op > (with_args ? Require::AtMostArg : Require::Present))
+      throw std::invalid_argument("capjwt: an unknown requirement op");
   }
 }
 bool scan_byte_ok(unsigned char c) { return c >= 0x20 && c <= 0x7e && c != '"' && c != '\\'; }
 
-MatchPlan::MatchPlan(const std::vector<Require>& reqs) : reqs(reqs), bit(reqs.size(), -1) {
-  check_requires(reqs);
+// how a requirement's other side travels in jg_preds::values: the text, the column (one byte), or the bound
+std::string pred_value(const Require& r) {
+  switch (r.op) {
+    case Require::Present: return std::string();
+    case Require::EqualsArg: case Require::AtLeastArg: case Require::AtMostArg: return std::string(1, (char)r.column);
+    case Require::AtLeast: case Require::AtMost: {
+      std::string v(8, '\0');
+      for (int b = 0; b < 8; ++b) v[b] = (char)((uint64_t)r.bound >> (8 * b));
+      return v;
+    }
+    default: return r.value;
+  }
+}
+
+const std::vector<std::vector<std::string_view>> kNoStrs;
+const std::vector<const int64_t*> kNoNums;
+MatchPlan::MatchPlan(const std::vector<Require>& reqs) : MatchPlan(reqs, 0, kNoStrs, kNoNums, false) {}
+
+MatchPlan::MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vector<std::vector<std::string_view>>& strs_,
+                     const std::vector<const int64_t*>& nums_, bool with_args_)
+    : reqs(reqs), bit(reqs.size(), -1), with_args(with_args_), strs(&strs_), nums(&nums_) {
+  const bool plain = !with_args;                      // MatchBatch's rules: ops 1..4 only
+  check_requires(reqs, !plain);
+  for (const Require& r : reqs) {
+    if (r.op == Require::EqualsArg && r.column >= strs_.size())
+      throw std::invalid_argument("capjwt: a requirement names a string column that was not given");
+    if ((r.op == Require::AtLeastArg || r.op == Require::AtMostArg) && r.column >= nums_.size())
+      throw std::invalid_argument("capjwt: a requirement names a number column that was not given");
+  }
+  for (const auto& col : strs_) {
+    if (col.size() != n) throw std::invalid_argument("capjwt: a string column does not hold one operand per token");
+  }
+  for (const int64_t* col : nums_)
+    if (!col && n) throw std::invalid_argument("capjwt: a number column does not hold one operand per token");
+  if (strs_.size() > JG_MAX_ARGS || nums_.size() > JG_MAX_ARGS) usable = false;
   std::vector<const ClaimPath*> upaths;
   std::vector<size_t> upreds;                        // the first requirement of each distinct one
   std::vector<int> path_of(reqs.size(), -1);
@@ -2817,8 +2873,8 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs) : reqs(reqs), bit(reqs.si
       for (unsigned char c : comp)
         if (!scan_byte_ok(c)) usable = false;
     }
-    // Present ignores its value on both paths
-    const size_t vlen = r.op == Require::Present ? 0 : r.value.size();
+    // Present ignores its value on both paths; an operand or a bound is no text
+    const size_t vlen = r.op >= Require::Present ? 0 : r.value.size();
     if (vlen > JG_PRED_VALUE_MAX) usable = false;
     if ((r.op == Require::HasWord || r.op == Require::HasElement) && vlen == 0) usable = false;
     for (size_t b = 0; b < vlen; ++b)
@@ -2830,14 +2886,19 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs) : reqs(reqs), bit(reqs.si
     size_t q = 0;
     for (; q < upreds.size(); ++q) {
       const Require& o = reqs[upreds[q]];
-      if (path_of[upreds[q]] == path_of[k] && o.op == r.op && (r.op == Require::Present || o.value == r.value)) break;
+      if (path_of[upreds[q]] == path_of[k] && o.op == r.op && pred_value(o) == pred_value(r)) break;
     }
     if (q == upreds.size()) upreds.push_back(k);
     bit[k] = (int)q;
     identity = identity && q == k;
   }
   if (upaths.size() > JG_MAX_PATHS) usable = false;
-  if (!usable) return;
+  if (!usable) {                                     // every token takes the host path; a NUL still throws
+    for (const auto& col : strs_)
+      for (const std::string_view v : col)
+        if (v.find('\0') != std::string_view::npos) throw std::invalid_argument("capjwt: an operand holds a NUL byte");
+    return;
+  }
   for (size_t u = 0; u < upaths.size(); ++u) {
     paths.ncomp[u] = (uint32_t)upaths[u]->size();
     for (size_t d = 0; d < upaths[u]->size(); ++d) {
@@ -2851,16 +2912,71 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs) : reqs(reqs), bit(reqs.si
     const Require& r = reqs[upreds[q]];
     preds.path[q] = (uint8_t)path_of[upreds[q]];
     preds.op[q] = (uint8_t)r.op;
-    preds.value_len[q] = r.op == Require::Present ? 0u : (uint32_t)r.value.size();
-    if (r.op != Require::Present) values += r.value;
+    const std::string v = pred_value(r);
+    preds.value_len[q] = (uint32_t)v.size();
+    values += v;
   }
   preds.n = (uint32_t)upreds.size();
   preds.values = (const uint8_t*)values.data();
+  if (plain) return;
+  // the operands, job-major; a token with an operand the scan refuses keeps empty spans and is not scanned
+  const size_t ns = strs_.size(), nn = nums_.size();
+  host_only.assign(n, 0);
+  aspans.assign(n * ns, jg_sarg{0, 0});
+  anums.resize(n * nn);
+  // count, prefix, fill over fixed ranges: a range's operands lie back to back from the range's own offset
+  const Chunks ch = make_chunks(n, host_threads());
+  std::vector<size_t> base(ch.count() + 1, 0);
+  std::atomic<bool> nul{false};
+  run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
+    size_t bytes = 0;
+    for (size_t i = lo; i < hi; ++i) {
+      bool ok = true;
+      size_t mine = 0;
+      for (size_t k = 0; k < ns; ++k) {
+        const std::string_view v = strs_[k][i];
+        if (v.find('\0') != std::string_view::npos) nul.store(true, std::memory_order_relaxed);
+        ok = ok && v.size() <= JG_PRED_VALUE_MAX;
+        for (size_t b = 0; ok && b < v.size(); ++b) ok = scan_byte_ok((unsigned char)v[b]);
+        mine += v.size();
+      }
+      host_only[i] = ok ? 0 : 1;
+      bytes += ok ? mine : 0;
+    }
+    base[c + 1] = bytes;
+  });
+  if (nul.load()) throw std::invalid_argument("capjwt: an operand holds a NUL byte");
+  for (size_t c = 0; c < ch.count(); ++c) base[c + 1] += base[c];
+  if (base[ch.count()] > 0xffffffffu) {               // the spans are 32 bits
+    usable = false;
+    return;
+  }
+  abytes.resize(base[ch.count()]);
+  run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
+    size_t o = base[c];
+    for (size_t i = lo; i < hi; ++i) {
+      for (size_t k = 0; k < ns && !host_only[i]; ++k) {
+        const std::string_view v = strs_[k][i];
+        aspans[i * ns + k] = jg_sarg{(uint32_t)o, (uint32_t)v.size()};
+        std::memcpy(&abytes[o], v.data(), v.size());
+        o += v.size();
+      }
+      for (size_t k = 0; k < nn; ++k) anums[i * nn + k] = nums_[k][i];
+    }
+  });
+  args.bytes = (const uint8_t*)abytes.data();
+  args.bytes_len = abytes.size();
+  args.str = aspans.data();
+  args.num = anums.data();
+  args.nstr = (uint32_t)ns;
+  args.nnum = (uint32_t)nn;
 }
 }  // namespace
 
-uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs) {
-  check_requires(reqs);
+namespace {
+// the requirements on a claims map; strs / nums: one token's operands, for the ops that take one
+uint32_t requires_on(const json::Value& all_claims, const std::vector<Require>& reqs, const std::string_view* strs,
+                     const int64_t* nums) {
   uint32_t bits = 0;
   for (size_t k = 0; k < reqs.size(); ++k) {
     const Require& r = reqs[k];
@@ -2894,10 +3010,49 @@ uint32_t match_requires(const json::Value& all_claims, const std::vector<Require
           for (const json::Value& e : v->arr)
             if (e.kind == json::Value::String && e.str.view() == r.value) { hit = true; break; }
         break;
+      case Require::EqualsArg: hit = v->kind == json::Value::String && v->str.view() == strs[r.column]; break;
+      // f, ok := v.(float64); ok && f >= float64(B)
+      case Require::AtLeast: hit = v->kind == json::Value::Number && v->num >= (double)r.bound; break;
+      case Require::AtMost: hit = v->kind == json::Value::Number && v->num <= (double)r.bound; break;
+      case Require::AtLeastArg: hit = v->kind == json::Value::Number && v->num >= (double)nums[r.column]; break;
+      case Require::AtMostArg: hit = v->kind == json::Value::Number && v->num <= (double)nums[r.column]; break;
     }
     if (hit) bits |= 1u << k;
   }
   return bits;
+}
+
+uint32_t MatchPlan::host_bits(const json::Value& claims, size_t i) const {
+  std::string_view s[JG_MAX_ARGS * 4];               // a list over the caps may hold more columns than the scan takes
+  int64_t v[JG_MAX_ARGS * 4];
+  if (strs->size() > JG_MAX_ARGS * 4 || nums->size() > JG_MAX_ARGS * 4) {
+    std::vector<std::string_view> sv(strs->size());
+    std::vector<int64_t> nv(nums->size());
+    for (size_t c = 0; c < sv.size(); ++c) sv[c] = (*strs)[c][i];
+    for (size_t c = 0; c < nv.size(); ++c) nv[c] = (*nums)[c][i];
+    return requires_on(claims, reqs, sv.data(), nv.data());
+  }
+  for (size_t c = 0; c < strs->size(); ++c) s[c] = (*strs)[c][i];
+  for (size_t c = 0; c < nums->size(); ++c) v[c] = (*nums)[c][i];
+  return requires_on(claims, reqs, s, v);
+}
+}  // namespace
+
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs) {
+  check_requires(reqs);
+  return requires_on(all_claims, reqs, nullptr, nullptr);
+}
+
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs,
+                        const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums) {
+  check_requires(reqs, true);
+  for (const Require& r : reqs) {
+    if (r.op == Require::EqualsArg && r.column >= strs.size())
+      throw std::invalid_argument("capjwt: a requirement names a string column that was not given");
+    if ((r.op == Require::AtLeastArg || r.op == Require::AtMostArg) && r.column >= nums.size())
+      throw std::invalid_argument("capjwt: a requirement names a number column that was not given");
+  }
+  return requires_on(all_claims, reqs, strs.data(), nums.data());
 }
 
 std::vector<MatchResult> Validator::MatchBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
@@ -2952,13 +3107,74 @@ void Validator::MatchVerdictsEach(const std::vector<std::string_view>& tokens, c
                                }, nullptr, nullptr, &plan);
 }
 
+std::vector<MatchResult> Validator::MatchBatchArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                                   const std::vector<Require>& requires_,
+                                                   const std::vector<std::vector<std::string_view>>& strs,
+                                                   const std::vector<const int64_t*>& nums, CheckStats* stats) {
+  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+  std::vector<MatchResult> out(tokens.size());
+  check_core<kMatchMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
+                                [&](size_t i, bool ok, std::string&& err, uint32_t bits) {
+                                  out[i].ok = ok;
+                                  out[i].err = std::move(err);
+                                  out[i].bits = bits;
+                                }, nullptr, nullptr, &plan);
+  return out;
+}
+
+void Validator::MatchVerdictsArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                  const std::vector<Require>& requires_,
+                                  const std::vector<std::vector<std::string_view>>& strs,
+                                  const std::vector<const int64_t*>& nums, uint8_t* ok_out, uint32_t* bits_out,
+                                  CheckStats* stats) {
+  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+  check_core<kMatchMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
+                                [&](size_t i, bool ok, std::string&&, uint32_t bits) {
+                                  ok_out[i] = ok ? 1 : 0;
+                                  bits_out[i] = bits;
+                                }, nullptr, nullptr, &plan);
+}
+
+std::vector<MatchResult> Validator::MatchBatchArgsEach(const std::vector<std::string_view>& tokens,
+                                                       const std::vector<Expected>& expected,
+                                                       const std::vector<uint32_t>& which,
+                                                       const std::vector<Require>& requires_,
+                                                       const std::vector<std::vector<std::string_view>>& strs,
+                                                       const std::vector<const int64_t*>& nums, CheckStats* stats) {
+  each_args("MatchBatchArgsEach", tokens, expected, which);
+  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+  std::vector<MatchResult> out(tokens.size());
+  check_core<kMatchMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                               [&](size_t i, bool ok, std::string&& err, uint32_t bits) {
+                                 out[i].ok = ok;
+                                 out[i].err = std::move(err);
+                                 out[i].bits = bits;
+                               }, nullptr, nullptr, &plan);
+  return out;
+}
+
+void Validator::MatchVerdictsArgsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                                      const std::vector<uint32_t>& which, const std::vector<Require>& requires_,
+                                      const std::vector<std::vector<std::string_view>>& strs,
+                                      const std::vector<const int64_t*>& nums, uint8_t* ok_out, uint32_t* bits_out,
+                                      CheckStats* stats) {
+  each_args("MatchVerdictsArgsEach", tokens, expected, which);
+  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+  check_core<kMatchMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
+                               [&](size_t i, bool ok, std::string&&, uint32_t bits) {
+                                 ok_out[i] = ok ? 1 : 0;
+                                 bits_out[i] = bits;
+                               }, nullptr, nullptr, &plan);
+}
+
 // The claims entries are the ones the host layer binds weakly: an ABI provider
 // without them (the stub ABI the CPU unit tests link, an older libcapjwt.so)
 // still links, and a CheckBatch against it reports the scan as unavailable, as
 // any other device failure.  jg_claims_scan (CheckBatch), jg_claims_extract
 // (RegisteredBatch), jg_claims_select (SelectBatch), jg_claims_each (the *Each
 // entries: the three scans with a profile per job), jg_claims_paths (the
-// Select entries by path) and jg_claims_match (the Match entries).
+// Select entries by path), jg_claims_match (the Match entries) and
+// jg_claims_match_args (the MatchArgs entries).
 extern "C" {
 __attribute__((weak)) int jg_claims_scan(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                          uint8_t*);
@@ -2972,6 +3188,9 @@ __attribute__((weak)) int jg_claims_paths(jg_ctx*, const uint8_t*, size_t, const
                                           uint32_t, const jg_paths*, uint8_t*, jg_claims*, jg_selected*);
 __attribute__((weak)) int jg_claims_match(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                           uint32_t, const jg_paths*, const jg_preds*, uint8_t*, uint32_t*);
+__attribute__((weak)) int jg_claims_match_args(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                               uint32_t, const jg_paths*, const jg_preds*, const jg_args*, uint8_t*,
+                                               uint32_t*);
 }
 
 void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
@@ -3021,6 +3240,15 @@ void Engine::claims_match(const uint8_t* arena, size_t arena_len, const void* jo
   abi_call("jg_claims_match", jg_claims_match != nullptr, inside_verify, [&] {
     return jg_claims_match(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
                            (const jg_paths*)paths, (const jg_preds*)preds, codes, masks);
+  });
+}
+
+void Engine::claims_match_args(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs,
+                               const void* expects, uint32_t nexpect, const void* paths, const void* preds,
+                               const void* args, uint8_t* codes, uint32_t* masks, bool inside_verify) {
+  abi_call("jg_claims_match_args", jg_claims_match_args != nullptr, inside_verify, [&] {
+    return jg_claims_match_args(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                                (const jg_paths*)paths, (const jg_preds*)preds, (const jg_args*)args, codes, masks);
   });
 }
 

@@ -219,6 +219,10 @@ class Engine {
   void claims_match(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                     uint32_t nexpect, const void* paths, const void* preds, uint8_t* codes, uint32_t* masks,
                     bool inside_verify = false);
+  // ... with the jobs' own operands (`args`, a jg_args) for the ops that take one (jg_claims_match_args)
+  void claims_match_args(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                         uint32_t nexpect, const void* paths, const void* preds, const void* args, uint8_t* codes,
+                         uint32_t* masks, bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -512,12 +516,22 @@ struct ClaimPaths {
 //   HasElement  v is an array and one of its direct elements is a string equal
 //               to `value`
 //   Present     the path reaches a value (null counts); `value` is unused
+// ... and, for the MatchBatchArgs entries only, with the token's own operands:
+//   EqualsArg   v is a string equal to the token's entry in string column `column`
+//   AtLeast     v is a number f with f >= float64(bound); AtMost: f <= float64(bound)
+//   AtLeastArg  AtLeast with the token's entry in number column `column` as the
+//               bound; AtMostArg likewise
 // The numbers are jg_pred_op's (include/jg.h).
 struct Require {
-  enum Op : uint8_t { Equals = 1, HasWord = 2, HasElement = 3, Present = 4 };
+  enum Op : uint8_t {
+    Equals = 1, HasWord = 2, HasElement = 3, Present = 4,
+    EqualsArg = 5, AtLeast = 6, AtMost = 7, AtLeastArg = 8, AtMostArg = 9
+  };
   ClaimPath path;
   Op op = Present;
   std::string value;
+  int64_t bound = 0;
+  uint32_t column = 0;
 };
 // At most this many per call: the mask has one bit per requirement (JG_MAX_PRED)
 constexpr size_t kMaxRequires = 16;
@@ -675,6 +689,39 @@ class Validator {
   void MatchVerdictsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
                          const std::vector<uint32_t>& which, const std::vector<Require>& requires_, uint8_t* ok,
                          uint32_t* bits, CheckStats* stats = nullptr);
+  // MatchBatch for the checks whose other side differs from token to token (the
+  // nonce of that request, auth_time under its max_age, sub against the session's
+  // subject): `strs` holds the string columns and `nums` the number columns, each
+  // with one entry per token, and a requirement may be EqualsArg, AtLeast, AtMost,
+  // AtLeastArg or AtMostArg (jg_claims_match_args).  The device decides a numeric
+  // requirement on an integer literal of at most 15 digits; a token whose number
+  // is written otherwise (a fraction, more digits) is left to the host path, which
+  // compares the float64 as Go does.  A token whose own string operand the scan
+  // does not take (a byte outside 0x20..0x7e, a quote, a backslash, over
+  // JG_PRED_VALUE_MAX bytes) takes the host path too; a list over the scan's caps
+  // (MatchBatch's, or more than JG_MAX_ARGS columns of a kind) sends every token
+  // there.  Results never depend on the caps.  Throws std::invalid_argument for
+  // what MatchBatch throws for (an unknown op is one outside 1..9), a column whose
+  // length is not the number of tokens, a column index without a column, and a
+  // NUL byte in an operand.
+  std::vector<MatchResult> MatchBatchArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
+                                          const std::vector<Require>& requires_,
+                                          const std::vector<std::vector<std::string_view>>& strs,
+                                          const std::vector<const int64_t*>& nums, CheckStats* stats = nullptr);
+  void MatchVerdictsArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
+                         const std::vector<Require>& requires_, const std::vector<std::vector<std::string_view>>& strs,
+                         const std::vector<const int64_t*>& nums, uint8_t* ok, uint32_t* bits,
+                         CheckStats* stats = nullptr);
+  std::vector<MatchResult> MatchBatchArgsEach(const std::vector<std::string_view>& tokens,
+                                              const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
+                                              const std::vector<Require>& requires_,
+                                              const std::vector<std::vector<std::string_view>>& strs,
+                                              const std::vector<const int64_t*>& nums, CheckStats* stats = nullptr);
+  void MatchVerdictsArgsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
+                             const std::vector<uint32_t>& which, const std::vector<Require>& requires_,
+                             const std::vector<std::vector<std::string_view>>& strs,
+                             const std::vector<const int64_t*>& nums, uint8_t* ok, uint32_t* bits,
+                             CheckStats* stats = nullptr);
  private:
   KeySet* ks_;
 };
@@ -695,6 +742,10 @@ Result validate_claims(const json::Value& all_claims, const TokenView& info, con
 // when requires[k] holds.  What the host path of MatchBatch runs; exposed for
 // tests.  Throws as MatchBatch does.
 uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& requires_);
+// ... and of a MatchBatchArgs call with one token's operands: strs[c] and nums[c]
+// are its entries in column c.  What the host path of MatchBatchArgs runs.
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& requires_,
+                        const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums);
 // Expected's three leeways after Go's defaulting (jwt/jwt.go:128-170): the
 // clock skew in ns (negative -> 0, 0 -> one minute) and the leeways that
 // default a missing exp / nbf, as the whole seconds Go adds (negative -> 0,

@@ -246,6 +246,34 @@ std::vector<uint32_t> which_of(const py::buffer& b) {
   return std::vector<uint32_t>(p, p + info.size);
 }
 
+// A column of n int64 operands (MatchBatchArgs' nums): any contiguous buffer of int64
+const int64_t* int64_column(const py::buffer_info& info, size_t n) {
+  if (info.itemsize != 8 || (info.format != "q" && info.format != "l" && info.format != "=q" && info.format != "<q"))
+    throw py::value_error("a number column must be a buffer of int64");
+  if (info.ndim != 1 || (info.size > 0 && info.strides[0] != 8))
+    throw py::value_error("a number column must be contiguous, one dimension");
+  if ((size_t)info.size != n) throw py::value_error("a number column does not hold one operand per token");
+  return (const int64_t*)info.ptr;
+}
+
+// A column of string operands as newline-separated bytes (MatchBlobArgs' strs): every piece between newlines is
+// an operand, empty ones too.  One newline after the last operand is allowed: an empty piece beyond the one per
+// token is dropped.
+std::vector<std::string_view> split_operands(const char* p, size_t n, size_t ntokens) {
+  std::vector<std::string_view> v;
+  v.reserve(ntokens + 1);
+  const char* const end = p + n;
+  for (;;) {
+    const char* nl = static_cast<const char*>(std::memchr(p, '\n', (size_t)(end - p)));
+    const char* e = nl ? nl : end;
+    v.emplace_back(p, (size_t)(e - p));
+    if (!nl) break;
+    p = nl + 1;
+  }
+  if (v.size() == ntokens + 1 && v.back().empty()) v.pop_back();
+  return v;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_capjwt_host, m) {
@@ -390,6 +418,22 @@ PYBIND11_MODULE(_capjwt_host, m) {
     std::vector<Require> rq;
     for (const auto& [path, op, value] : reqs) rq.push_back(Require{path, (Require::Op)op, value});
     return match_requires(v, rq);
+  });
+  m.def("match_requires_args", [](py::bytes payload,
+                                  const std::vector<std::tuple<ClaimPath, int, std::string, int64_t, uint32_t>>& reqs,
+                                  const std::vector<std::string>& strs, const std::vector<int64_t>& nums) {
+    // the host path of MatchBatchArgs with one token's operands: the mask
+    json::Value v;
+    std::string err;
+    if (!json::parse(std::string(payload), &v, &err)) throw py::value_error(err);
+    std::vector<Require> rq;
+    for (const auto& [path, op, value, bound, column] : reqs)
+      rq.push_back(Require{path, (Require::Op)op, value, bound, column});
+    try {
+      return match_requires(v, rq, std::vector<std::string_view>(strs.begin(), strs.end()), nums);
+    } catch (const std::invalid_argument& e) {
+      throw py::value_error(e.what());
+    }
   });
   m.def("host_threads", &host_threads);
   m.def("set_host_memory_retention", &SetHostMemoryRetention);
@@ -713,6 +757,79 @@ PYBIND11_MODULE(_capjwt_host, m) {
     d["match"] = match;
     return py::make_tuple(d, st.scanned, st.host);
   };
+  // a requirement of the MatchArgs entries: (path, op, value, bound, column)
+  using ArgReqList = std::vector<std::tuple<ClaimPath, int, std::string, int64_t, uint32_t>>;
+  auto arg_requires_of = [](const ArgReqList& reqs) {
+    std::vector<Require> rq;
+    rq.reserve(reqs.size());
+    for (const auto& [path, op, value, bound, column] : reqs)
+      rq.push_back(Require{path, (Require::Op)op, value, bound, column});
+    return rq;
+  };
+  // the number columns of a call: the buffers stay requested (and so alive) for its duration
+  struct NumCols {
+    std::vector<py::buffer_info> infos;
+    std::vector<const int64_t*> cols;
+    NumCols(const std::vector<py::buffer>& nums, size_t n) {
+      for (const py::buffer& b : nums) {
+        infos.push_back(b.request());
+        cols.push_back(int64_column(infos.back(), n));
+      }
+    }
+  };
+  auto py_match_batch_args = [=](PyValidator& s, py::sequence toks, const ArgReqList& reqs,
+                                 const std::vector<std::vector<std::string>>& strs, const std::vector<py::buffer>& nums,
+                                 const Who& who) {
+    // match_batch with the tokens' own operands: strs[c][i] and nums[c][i] are token i's in column c
+    auto v = as_strings(toks);
+    const std::vector<Require> rq = arg_requires_of(reqs);
+    std::vector<std::vector<std::string_view>> sv;
+    for (const auto& col : strs) sv.emplace_back(col.begin(), col.end());
+    const NumCols nc(nums, v.size());
+    std::vector<MatchResult> rs;
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      rs = who.es ? s.v->MatchBatchArgsEach(views(v), *who.es, *who.w, rq, sv, nc.cols, &st)
+                  : s.v->MatchBatchArgs(views(v), *who.e, rq, sv, nc.cols, &st);
+    }
+    py::list out(rs.size());
+    for (size_t i = 0; i < rs.size(); ++i) {
+      if (rs[i].ok) out[i] = py::make_tuple(py::int_(rs[i].bits), py::none());
+      else out[i] = py::make_tuple(py::none(), py::str(rs[i].err));
+    }
+    return py::make_tuple(out, st.scanned, st.host);
+  };
+  auto py_match_blob_args = [=](PyValidator& s, py::bytes blob, const ArgReqList& reqs, const std::vector<py::bytes>& strs,
+                                const std::vector<py::buffer>& nums, const Who& who) {
+    // match_blob with the tokens' own operands: a string column is newline-separated bytes, as the tokens are
+    char* bp = nullptr;
+    Py_ssize_t bn = 0;
+    if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
+    const std::vector<Require> rq = arg_requires_of(reqs);
+    auto toks = split_lines(bp, (size_t)bn);
+    std::vector<std::vector<std::string_view>> sv;
+    for (const py::bytes& col : strs) {
+      char* cp = nullptr;
+      Py_ssize_t cn = 0;
+      if (PyBytes_AsStringAndSize(col.ptr(), &cp, &cn) != 0) throw py::error_already_set();
+      sv.push_back(split_operands(cp, (size_t)cn, toks.size()));
+    }
+    const NumCols nc(nums, toks.size());
+    py::bytes ok = fresh_bytes(toks.size()), match = fresh_bytes(4 * toks.size());
+    uint8_t* const okp = (uint8_t*)bytes_mem(ok);
+    uint32_t* const mp = (uint32_t*)bytes_mem(match);
+    CheckStats st;
+    {
+      py::gil_scoped_release rel;
+      if (who.es) s.v->MatchVerdictsArgsEach(toks, *who.es, *who.w, rq, sv, nc.cols, okp, mp, &st);
+      else s.v->MatchVerdictsArgs(toks, *who.e, rq, sv, nc.cols, okp, mp, &st);
+    }
+    py::dict d;
+    d["ok"] = ok;
+    d["match"] = match;
+    return py::make_tuple(d, st.scanned, st.host);
+  };
   py::class_<PyValidator>(m, "Validator")
       .def(py::init([](PyKeySet* ks) {
         if (!ks) throw py::value_error("keySet must not be nil");
@@ -844,6 +961,25 @@ PYBIND11_MODULE(_capjwt_host, m) {
                                 const std::vector<Expected>& es, py::buffer which) {
         const std::vector<uint32_t> w = which_of(which);
         return py_match_blob(s, blob, reqs, Who{nullptr, &es, &w});
+      })
+      .def("match_batch_args", [=](PyValidator& s, py::sequence toks, ArgReqList reqs,
+                                   std::vector<std::vector<std::string>> strs, std::vector<py::buffer> nums,
+                                   const Expected& e) {
+        return py_match_batch_args(s, toks, reqs, strs, nums, Who{&e, nullptr, nullptr});
+      })
+      .def("match_batch_args_each", [=](PyValidator& s, py::sequence toks, ArgReqList reqs,
+                                        std::vector<std::vector<std::string>> strs, std::vector<py::buffer> nums,
+                                        const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
+        return py_match_batch_args(s, toks, reqs, strs, nums, Who{nullptr, &es, &which});
+      })
+      .def("match_blob_args", [=](PyValidator& s, py::bytes blob, ArgReqList reqs, std::vector<py::bytes> strs,
+                                  std::vector<py::buffer> nums, const Expected& e) {
+        return py_match_blob_args(s, blob, reqs, strs, nums, Who{&e, nullptr, nullptr});
+      })
+      .def("match_blob_args_each", [=](PyValidator& s, py::bytes blob, ArgReqList reqs, std::vector<py::bytes> strs,
+                                       std::vector<py::buffer> nums, const std::vector<Expected>& es, py::buffer which) {
+        const std::vector<uint32_t> w = which_of(which);
+        return py_match_blob_args(s, blob, reqs, strs, nums, Who{nullptr, &es, &w});
       })
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {

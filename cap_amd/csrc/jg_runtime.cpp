@@ -720,6 +720,7 @@ struct Device {
   Grow cl_profiles;                 // jg_claims_each's resolved table
   Grow cl_paths;                    // jg_claims_paths' resolved paths
   Grow cl_preds, cl_match;          // jg_claims_match's resolved predicates and its masks
+  Grow cl_abytes, cl_astr, cl_anum; // jg_claims_match_args' operands: the bytes, the span table, the numbers
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -3469,7 +3470,7 @@ int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
 
 namespace {
 
-// One scan of the claims: what the six jg_claims_* entries hand to claims_run.
+// One scan of the claims: what the seven jg_claims_* entries hand to claims_run.
 // The resolved sides are host objects that `resolve` fills and points these at;
 // each is uploaded into the kept device buffer of its kind, and the kernel is
 // picked from which of them, and which outputs, are there (launch_claims).
@@ -3487,6 +3488,8 @@ struct ClaimsCall {
   const jgclaims::Paths* paths = nullptr;
   const jgclaims::Preds* preds = nullptr;       // with paths and match_out: the masks in the place of the records
   uint32_t* match_out = nullptr;
+  const jgclaims::ArgPreds* apreds = nullptr;   // in the place of preds, with args: the jobs' own operands
+  const jg_args* args = nullptr;
 };
 
 const char kRefuseExpect[] = "more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9";
@@ -3504,6 +3507,13 @@ const char kRefusePreds[] =
     "more than 16 predicates, a path index past the paths, an unknown op, a value that is "
     "over 64 bytes, empty for HAS_WORD or HAS_ELEMENT, not empty for PRESENT or not printable "
     "ASCII without quote and backslash, a space in a HAS_WORD value, or two identical predicates";
+
+const char kRefuseArgPreds[] =
+    "more than 16 predicates, a path index past the paths, an op outside 1..9, a value that is "
+    "over 64 bytes, empty for HAS_WORD or HAS_ELEMENT, not empty for PRESENT or not printable "
+    "ASCII without quote and backslash, a space in a HAS_WORD value, more than 4 string or number "
+    "columns, a column index that is not one byte below its count, a bound that is not 8 bytes, "
+    "or two identical predicates";
 
 // The one path of a scan, after the entry's own NULL-argument test.  `resolve`
 // is the entry's resolve step: it fills the call's resolved sides and returns
@@ -3555,8 +3565,23 @@ int claims_run(jg_ctx* ctx, const std::string& entry, ClaimsCall& c, const std::
     if (c.vals_out) L.vals_out = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
     if (c.sel_out) L.sel_out = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
     if (c.match_out) {
-      L.preds = (const jgclaims::Preds*)upload(d->cl_preds, c.preds, sizeof *c.preds);
+      if (c.apreds) L.apreds = (const jgclaims::ArgPreds*)upload(d->cl_preds, c.apreds, sizeof *c.apreds);
+      else L.preds = (const jgclaims::Preds*)upload(d->cl_preds, c.preds, sizeof *c.preds);
       L.match_out = (uint32_t*)d->cl_match.get(sizeof(uint32_t) * njobs);
+    }
+    if (c.apreds) {
+      // the operands: the bytes with the arena's slack behind them (the kernel reads them by aligned words)
+      const jg_args& A = *c.args;
+      uint8_t* ab = (uint8_t*)d->cl_abytes.get(A.bytes_len + ARENA_SLACK);
+      HIPCHK(hipMemsetAsync(ab + A.bytes_len, 0, ARENA_SLACK, s));
+      if (A.bytes_len) HIPCHK(hipMemcpyAsync(ab, A.bytes, A.bytes_len, hipMemcpyHostToDevice, s));
+      L.arg_bytes = ab;
+      L.arg_str = (const jg_sarg*)d->cl_astr.get(sizeof(jg_sarg) * njobs * A.nstr);
+      if (A.nstr) HIPCHK(hipMemcpyAsync((void*)L.arg_str, A.str, sizeof(jg_sarg) * njobs * A.nstr, hipMemcpyHostToDevice, s));
+      L.arg_num = (const int64_t*)d->cl_anum.get(sizeof(int64_t) * njobs * A.nnum);
+      if (A.nnum) HIPCHK(hipMemcpyAsync((void*)L.arg_num, A.num, sizeof(int64_t) * njobs * A.nnum, hipMemcpyHostToDevice, s));
+      L.nstr = A.nstr;
+      L.nnum = A.nnum;
     }
     launch_claims(L, s);
     HIPCHK(hipGetLastError());
@@ -3678,6 +3703,42 @@ int jg_claims_match(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     c.table = T.get();
     c.paths = P.get();
     c.preds = Q.get();
+    c.match_out = match_out;
+    return nullptr;
+  });
+}
+
+// jg_claims_match whose predicates may take an operand of the job's own or test
+// a number: the resolved predicates in their wider form, and three more uploads
+// (the operand bytes, the span table, the numbers)
+int jg_claims_match_args(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                         const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
+                         const jg_paths* paths, const jg_preds* preds, const jg_args* args, uint8_t* code_out,
+                         uint32_t* match_out) {
+  if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out || !paths || !preds || !match_out || !args)) ||
+      (arena_len > 0 && !arena))
+    return -1;
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, nullptr, nullptr};
+  auto T = std::make_unique<jgclaims::Profiles>();
+  auto P = std::make_unique<jgclaims::Paths>();
+  auto Q = std::make_unique<jgclaims::ArgPreds>();
+  std::string why;
+  return claims_run(ctx, "jg_claims_match_args", c, [&]() -> const char* {
+    if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) return kRefuseProfiles;
+    if (!jgclaims::resolve_paths(*paths, P.get())) return kRefusePaths;
+    if (!jgclaims::resolve_arg_preds(*preds, *P, args->nstr, args->nnum, Q.get())) return kRefuseArgPreds;
+    if ((args->bytes_len && !args->bytes) || (args->nstr && !args->str) || (args->nnum && !args->num))
+      return "the operands' bytes, spans or numbers are NULL";
+    for (size_t i = 0; i < njobs; ++i) {
+      if (jgclaims::arg_operands_ok(*args, i)) continue;
+      why = "job " + std::to_string(i) + " has a string operand over 64 bytes, past the operand bytes or "
+            "with a byte that is not printable ASCII without quote and backslash";
+      return why.c_str();
+    }
+    c.table = T.get();
+    c.paths = P.get();
+    c.apreds = Q.get();
+    c.args = args;
     c.match_out = match_out;
     return nullptr;
   });

@@ -32,6 +32,27 @@ struct WordSrc {
   }
 };
 
+// One lane's operands (jg_claims_match_args) as the scan reads them: the row of
+// the span table and of the numbers that belongs to the lane's job, and the
+// operand bytes through aligned words, as WordSrc reads the arena: two word loads
+// per four compared bytes, never more than seven bytes past an operand (the
+// buffer has ARENA_SLACK behind it).  Nothing is kept in registers here: the
+// scan holds the lengths in one dword and a window per column.
+struct ArgSrc {
+  const uint32_t* words;      // the operand bytes
+  const jg_sarg* str;         // the lane's nstr spans
+  const int64_t* num;         // the lane's numbers
+  uint32_t ns;
+  __device__ __forceinline__ uint32_t nstr() const { return ns; }
+  __device__ __forceinline__ uint32_t slen(uint32_t c) const { return str[c].len; }
+  __device__ __forceinline__ uint32_t word(uint32_t c, uint32_t p) const {
+    const uint32_t a = str[c].off + p;
+    const uint32_t* q = words + (a >> 2);
+    return (uint32_t)((((uint64_t)q[1] << 32) | q[0]) >> (8u * (a & 3u)));
+  }
+  __device__ __forceinline__ int64_t bound(uint32_t c) const { return num[c]; }
+};
+
 constexpr int kBlock = 256;
 
 // the block copies `words` 32-bit words of *src, from word `first` on, to its LDS object *dst
@@ -61,7 +82,7 @@ __device__ __forceinline__ void store_selected(jg_selected* out, const jg_select
                     q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
 }
 
-// The body of all eight kernels.  M is the scan's mode.  X is the block's LDS
+// The body of all nine kernels.  M is the scan's mode.  X is the block's LDS
 // copy of the expected side, XS its type:
 //   Expect    one for the call, copied whole;
 //   Profiles  the call's table (jg_claims_each), copied only as far as it is in
@@ -73,14 +94,20 @@ __device__ __forceinline__ void store_selected(jg_selected* out, const jg_select
 // S is the LDS copy of what a selecting mode selects by, SL its type: Select's
 // names or, for kPath and kMatch, Paths.  The records stay in registers (fields
 // and constant indices only) until they are stored.  Q is the LDS copy of the
-// predicates of kMatch, which keeps no record: a byte and a dword per lane.
-template <int M, class XS, class SL>
+// predicates of kMatch and kMatchArgs (PQ: Preds or ArgPreds), which keep no
+// record: a byte and a dword per lane.  kMatchArgs also reads the lane's own
+// operands, from global memory (ArgSrc).
+template <int M, class XS, class SL, class PQ = Preds>
 __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restrict__ arena,
                                             const jg_cjob* __restrict__ jobs, int64_t n, const XS* __restrict__ expect,
                                             const SL* __restrict__ select, uint8_t* __restrict__ code_out,
                                             jg_claims* __restrict__ vals_out, jg_selected* __restrict__ sel_out,
-                                            Preds* Q = nullptr, const Preds* __restrict__ preds = nullptr,
-                                            uint32_t* __restrict__ match_out = nullptr) {
+                                            PQ* Q = nullptr, const PQ* __restrict__ preds = nullptr,
+                                            uint32_t* __restrict__ match_out = nullptr,
+                                            const uint8_t* __restrict__ arg_bytes = nullptr,
+                                            const jg_sarg* __restrict__ arg_str = nullptr,
+                                            const int64_t* __restrict__ arg_num = nullptr, uint32_t nstr = 0,
+                                            uint32_t nnum = 0) {
   constexpr bool kTable = std::is_same_v<XS, Profiles>;
   uint32_t np = 0;
   if constexpr (kTable) {
@@ -96,7 +123,7 @@ __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restr
     copy_words(&X, expect, 0u, sizeof(Expect) / 4u);
   }
   if constexpr (M >= kSelect) copy_words(S, select, 0u, sizeof(SL) / 4u);
-  if constexpr (M == kMatch) copy_words(Q, preds, 0u, sizeof(Preds) / 4u);
+  if constexpr (kPred<M>) copy_words(Q, preds, 0u, sizeof(PQ) / 4u);
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -108,7 +135,11 @@ __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restr
   jg_claims v;
   jg_selected q;
   uint32_t bits;
-  if constexpr (kTable) {
+  if constexpr (M == kMatchArgs) {
+    const ProfileRef E{X, J.flags < np ? J.flags : 0u};
+    const ArgSrc A{(const uint32_t*)arg_bytes, arg_str + i * nstr, arg_num + i * nnum, nstr};
+    code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q, Q, &bits, &A);
+  } else if constexpr (kTable) {
     const ProfileRef E{X, J.flags < np ? J.flags : 0u};                         // likewise: checked before the launch
     code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q, Q, &bits);
   } else {
@@ -116,7 +147,7 @@ __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restr
   }
   if constexpr (kRec<M>) store_claims(vals_out + i, v);
   if constexpr (kSel<M>) store_selected(sel_out + i, q);
-  if constexpr (M == kMatch) match_out[i] = bits;
+  if constexpr (kPred<M>) match_out[i] = bits;
 }
 
 // code_out[i] = the jg_claim_code of jobs[i]
@@ -220,6 +251,28 @@ __global__ void __launch_bounds__(kBlock) k_claims_match_each(const uint8_t* __r
                                        match_out);
 }
 
+// k_claims_match_each whose predicates may also take an operand of the lane's
+// own job (jg_claims_match_args) or test a number: the resolved predicates
+// (ArgPreds) sit in LDS in the place of Preds; job i's string operands are spans
+// arg_str[i * nstr + c] of arg_bytes and are compared from global memory, a
+// window of four bytes per column at a time; its numbers are arg_num[i * nnum + c].
+__global__ void __launch_bounds__(kBlock) k_claims_match_args(const uint8_t* __restrict__ arena,
+                                                              const jg_cjob* __restrict__ jobs, int64_t n,
+                                                              const Profiles* __restrict__ table,
+                                                              const Paths* __restrict__ paths,
+                                                              const ArgPreds* __restrict__ preds,
+                                                              const uint8_t* __restrict__ arg_bytes,
+                                                              const jg_sarg* __restrict__ arg_str,
+                                                              const int64_t* __restrict__ arg_num, uint32_t nstr,
+                                                              uint32_t nnum, uint8_t* __restrict__ code_out,
+                                                              uint32_t* __restrict__ match_out) {
+  __shared__ Profiles T;
+  __shared__ Paths P;
+  __shared__ ArgPreds Q;
+  claims_body<kMatchArgs, Profiles, Paths, ArgPreds>(T, &P, arena, jobs, n, table, paths, code_out, nullptr, nullptr, &Q,
+                                                     preds, match_out, arg_bytes, arg_str, arg_num, nstr, nnum);
+}
+
 }  // namespace
 
 void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
@@ -228,7 +281,10 @@ void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
   const auto go = [&](auto kernel, auto... rest) {
     hipLaunchKernelGGL(kernel, grid, block, 0, s, c.arena, c.jobs, c.n, rest...);
   };
-  if (c.match_out) go(k_claims_match_each, c.table, c.paths, c.preds, c.code_out, c.match_out);
+  if (c.apreds)
+    go(k_claims_match_args, c.table, c.paths, c.apreds, c.arg_bytes, c.arg_str, c.arg_num, c.nstr, c.nnum, c.code_out,
+       c.match_out);
+  else if (c.match_out) go(k_claims_match_each, c.table, c.paths, c.preds, c.code_out, c.match_out);
   else if (c.paths) go(k_claims_paths_each, c.table, c.paths, c.code_out, c.vals_out, c.sel_out);
   else if (c.table && c.sel_out) go(k_claims_select_each, c.table, c.select, c.code_out, c.vals_out, c.sel_out);
   else if (c.table && c.vals_out) go(k_claims_extract_each, c.table, c.code_out, c.vals_out);

@@ -43,6 +43,13 @@
 // value's first byte, narrowed per byte and resolved at the closing quote, as
 // `cand` is for the expected strings.
 //
+// claims_match_args() is a sixth mode (ScanT<kMatchArgs>): kMatch whose
+// predicates (ArgPreds, in the place of Preds) may compare a string with an
+// operand of the token's own -- read from global memory through a window of four
+// bytes per column, its length kept in a byte of one dword -- or a number with a
+// bound, the token's own or the list's: decided on integers of at most 15 digits
+// and left to the host (the one code a predicate changes) on any other number.
+//
 // The expected side is a template parameter of the scan (EX: slen / sbyte / auds
 // and the window's edges).  Expect is one; ProfileRef, one profile of a
 // Profiles table picked per token, is the other: claims_decide_each,
@@ -352,6 +359,108 @@ inline bool resolve_preds(const jg_preds& x, const Paths& P, Preds* Q) {
   return true;
 }
 
+// The predicates of jg_claims_match_args as its scan reads them: Preds' fields
+// under Preds' names (the scan reads either through the same code), and for the
+// five ops only that entry takes: the column of a predicate whose operand is the
+// lane's own, the constant numeric bounds, and per path the numeric predicates.
+// An ARG or numeric predicate has no bytes in the pool (len 0); EQUALS_ARG is in
+// `str` like EQUALS, so a string arms it.
+struct ArgPreds {
+  int64_t bound[JG_MAX_PRED];                         // NUM_GE / NUM_LE: B
+  uint32_t n;
+  uint16_t all[JG_MAX_PATHS], present[JG_MAX_PATHS], str[JG_MAX_PATHS], word[JG_MAX_PATHS], elem[JG_MAX_PATHS];
+  uint16_t num[JG_MAX_PATHS];                         // the numeric predicates on the path
+  uint16_t arg;                                       // the operand is the lane's: EQUALS_ARG, NUM_GE_ARG, NUM_LE_ARG
+  uint16_t le;                                        // NUM_LE and NUM_LE_ARG; the other numeric ones are >=
+  uint8_t op[JG_MAX_PRED];
+  uint8_t len[JG_MAX_PRED];
+  uint8_t col[JG_MAX_PRED];                           // the column of an ARG predicate
+  uint16_t off[JG_MAX_PRED];
+  uint8_t pool[JG_MAX_PRED * JG_PRED_VALUE_MAX];
+};
+static_assert(sizeof(ArgPreds) == 128 + 4 + 6 * 16 + 4 + 3 * 16 + 32 + 1024 && sizeof(ArgPreds) % 8 == 0,
+              "no padding in the predicates with operands");
+static_assert(JG_MAX_ARGS == 4 && JG_PRED_VALUE_MAX <= 255, "four operand lengths in one dword");
+
+// Fills *Q from the ABI's jg_preds as jg_claims_match_args reads it, for the
+// resolved paths P and the column counts of the same call.  Ops 1..4 are held to
+// resolve_preds' rules.  False also for: a column count over JG_MAX_ARGS, an
+// EQUALS_ARG or NUM_*_ARG whose value is not one byte below its column count, a
+// NUM_GE / NUM_LE whose value is not eight bytes (B, little-endian), two identical
+// predicates (for an ARG one: the same path, op and column).
+inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, uint32_t nnum, ArgPreds* Q) {
+  if (x.n > JG_MAX_PRED || nstr > JG_MAX_ARGS || nnum > JG_MAX_ARGS) return false;
+  *Q = ArgPreds{};
+  uint8_t path[JG_MAX_PRED] = {};
+  uint32_t vlen[JG_MAX_PRED] = {}, voff[JG_MAX_PRED] = {};        // within x.values
+  uint32_t o = 0, po = 0;                                         // within x.values, within the pool
+  for (uint32_t k = 0; k < x.n; ++k) {
+    const uint32_t p = x.path[k], op = x.op[k], l = x.value_len[k];
+    if (p >= P.n || op < JG_PRED_EQUALS || op > JG_PRED_NUM_LE_ARG) return false;
+    const bool konst = op <= JG_PRED_PRESENT;
+    const bool arg = op == JG_PRED_EQUALS_ARG || op == JG_PRED_NUM_GE_ARG || op == JG_PRED_NUM_LE_ARG;
+    const bool num = op >= JG_PRED_NUM_GE;
+    const uint32_t lo = konst ? (op == JG_PRED_EQUALS || op == JG_PRED_PRESENT ? 0u : 1u) : arg ? 1u : 8u;
+    const uint32_t hi = konst ? (op == JG_PRED_PRESENT ? 0u : (uint32_t)JG_PRED_VALUE_MAX) : lo;
+    if (l < lo || l > hi || (l && !x.values)) return false;
+    if (konst) {
+      for (uint32_t b = 0; b < l; ++b) {
+        const uint8_t c = x.values[o + b];
+        if (!name_byte_ok(c) || (op == JG_PRED_HAS_WORD && c == 0x20u)) return false;
+        Q->pool[po + b] = c;
+      }
+      Q->len[k] = (uint8_t)l;
+      Q->off[k] = (uint16_t)po;
+      po += l;
+    } else if (arg) {
+      if (x.values[o] >= (op == JG_PRED_EQUALS_ARG ? nstr : nnum)) return false;
+      Q->col[k] = x.values[o];
+    } else {
+      uint64_t b8 = 0;
+      for (uint32_t b = 0; b < 8u; ++b) b8 |= (uint64_t)x.values[o + b] << (8u * b);
+      Q->bound[k] = (int64_t)b8;
+    }
+    path[k] = (uint8_t)p;
+    Q->op[k] = (uint8_t)op;
+    vlen[k] = l;
+    voff[k] = o;
+    for (uint32_t j = 0; j < k; ++j) {
+      if (path[j] != p || Q->op[j] != op || vlen[j] != l) continue;
+      uint32_t b = 0;
+      while (b < l && x.values[voff[j] + b] == x.values[o + b]) ++b;
+      if (b == l) return false;
+    }
+    const uint16_t bit = (uint16_t)(1u << k);
+    Q->all[p] |= bit;
+    if (op == JG_PRED_PRESENT) Q->present[p] |= bit;
+    if (op == JG_PRED_EQUALS || op == JG_PRED_HAS_WORD || op == JG_PRED_EQUALS_ARG) Q->str[p] |= bit;
+    if (op == JG_PRED_HAS_WORD) Q->word[p] |= bit;
+    if (op == JG_PRED_HAS_ELEMENT) Q->elem[p] |= bit;
+    if (num) Q->num[p] |= bit;
+    if (arg) Q->arg |= bit;
+    if (op == JG_PRED_NUM_LE || op == JG_PRED_NUM_LE_ARG) Q->le |= bit;
+    o += l;
+  }
+  Q->n = x.n;
+  return true;
+}
+
+// One job's operands as jg_claims_match_args checks them before the launch:
+// every string operand within `bytes`, at most JG_PRED_VALUE_MAX bytes, each a
+// value's byte (name_byte_ok).  False: job i's operands are refused.
+inline bool arg_operands_ok(const jg_args& a, size_t i) {
+  for (uint32_t c = 0; c < a.nstr; ++c) {
+    const jg_sarg& s = a.str[i * a.nstr + c];
+    if (s.len > JG_PRED_VALUE_MAX || s.off > a.bytes_len || s.len > a.bytes_len - s.off) return false;
+    for (uint32_t b = 0; b < s.len; ++b)
+      if (!name_byte_ok(a.bytes[s.off + b])) return false;
+  }
+  return true;
+}
+
+// No operands: what the modes without them hand the scan
+struct NoArgs {};
+
 enum : uint32_t {
   ST_START, ST_VALUE, ST_ARR_FIRST, ST_OBJ_FIRST, ST_OBJ_KEY, ST_COLON, ST_AFTER, ST_STR,
   ST_NUM_MINUS, ST_NUM_ZERO, ST_NUM_INT, ST_NUM_DOT, ST_NUM_FRAC, ST_LIT, ST_DONE
@@ -421,19 +530,33 @@ struct MatchState {
   uint32_t res = 0;                 // the predicates that hold on what was read so far
 };
 
+// What the matching form with operands (claims_match_args) keeps beside
+// MatchState's.  An open string can be compared with at most one operand per
+// column (two predicates of one path, op and column are refused), so a window of
+// four operand bytes per column is enough; like SelState's slot arrays it is only
+// touched by constant-trip loops over all columns (selects on `col == c`).
+struct MatchArgsState : MatchState {
+  uint32_t alen = 0;                // the lane's string operands' lengths, a byte per column
+  uint32_t nump = 0;                // the numeric predicates of the member whose value is being read
+  uint32_t win[JG_MAX_ARGS] = {};   // per column: bytes [pos & ~3, (pos & ~3) + 4) of the lane's operand
+};
+
 // The scan's compile-time modes: the verdict alone, with the jg_claims record,
 // with the record and the caller's selected members (jg_selected) by name or by
-// path, and with the caller's predicates on members reached by path
-constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3, kMatch = 4;
-// what a mode keeps: the jg_claims record, the jg_selected record, the path matcher
+// path, with the caller's predicates on members reached by path, and with
+// predicates that also take an operand per token or test a number
+constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3, kMatch = 4, kMatchArgs = 5;
+// what a mode keeps: the jg_claims record, the jg_selected record, the path matcher, the predicates
 template <int M> constexpr bool kRec = M >= kExtract && M <= kPath;
 template <int M> constexpr bool kSel = M >= kSelect && M <= kPath;
-template <int M> constexpr bool kWalk = M == kPath || M == kMatch;
+template <int M> constexpr bool kWalk = M == kPath || M == kMatch || M == kMatchArgs;
+template <int M> constexpr bool kPred = M == kMatch || M == kMatchArgs;
 
 template <int M>
-struct ScanT : std::conditional_t<M == kMatch, MatchState, std::conditional_t<M == kPath, ExtractPath,
+struct ScanT : std::conditional_t<M == kMatchArgs, MatchArgsState,
+                                  std::conditional_t<M == kMatch, MatchState, std::conditional_t<M == kPath, ExtractPath,
                                   std::conditional_t<M == kSelect, ExtractSelect,
-                                  std::conditional_t<M == kExtract, Extract, NoExtract>>>> {
+                                  std::conditional_t<M == kExtract, Extract, NoExtract>>>>> {
   uint32_t st = ST_START;
   uint32_t depth = 0, stk = 0;      // open containers; bit d: container d+1 is an object
   uint32_t field = F_NONE;          // the top-level member whose value comes next
@@ -559,13 +682,13 @@ JG_CL_HD void pop(ScanT<M>& s, uint32_t is_obj) {
     }
   }
   if constexpr (kSel<M>) sel_end(s, s.dpos + 1u, 0u);          // the selected member's ] or }
-  if constexpr (M == kMatch) s.marr = s.depth < s.medepth ? 0u : s.marr;   // the selected array's ]
+  if constexpr (kPred<M>) s.marr = s.depth < s.medepth ? 0u : s.marr;   // the selected array's ]
   end_value(s);
 }
 
 // the first byte of a value
-template <int M, class EX>
-JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const Preds* Q = nullptr) {
+template <int M, class EX, class PQ = Preds>
+JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const PQ* Q = nullptr) {
   (void)Q;
   const uint32_t f = s.depth == 1u ? s.field : (uint32_t)F_NONE;
   const uint32_t elem = s.depth == 2u && s.aud_arr;        // an element of aud's array
@@ -574,7 +697,7 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const Preds* Q =
     s.md += c == '{' ? s.desc : 0u;
     s.desc = 0;
   }
-  if constexpr (M == kMatch) {
+  if constexpr (kPred<M>) {
     // The value of the member a path ends at (its key cleared the path's predicates), or a direct
     // element of that member's open array: PRESENT holds from here; a string arms the candidates.
     const uint32_t slot = path_slot(s);
@@ -587,6 +710,7 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const Preds* Q =
     s.mcand = !str ? 0u : slot ? Q->str[slot - 1u] : el ? Q->elem[el - 1u] : 0u;
     s.mword = str && slot ? Q->word[slot - 1u] : 0u;
     s.wpos = 0;
+    if constexpr (M == kMatchArgs) s.nump = slot ? Q->num[slot - 1u] : 0u;   // read by end_number, if this is one
     if (c == '[' && slot) {
       s.marr = slot;
       s.medepth = s.depth + 1u;
@@ -648,8 +772,10 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const Preds* Q =
 }
 
 // a number ended in front of the current byte
-template <int M>
-JG_CL_HD void end_number(ScanT<M>& s) {
+template <int M, class PQ = Preds, class AR = NoArgs>
+JG_CL_HD void end_number(ScanT<M>& s, const PQ* Q = nullptr, const AR* A = nullptr) {
+  (void)Q;
+  (void)A;
   if (s.isdate) {
     // -?(0|[1-9][0-9]{0,14}), not -0: exact in float64 and far from any wrap
     if (s.st != ST_NUM_ZERO && s.st != ST_NUM_INT) s.bad = 1;
@@ -661,16 +787,38 @@ JG_CL_HD void end_number(ScanT<M>& s) {
     s.iat = s.field == F_IAT ? v : s.iat;
     if constexpr (kRec<M>) s.present |= 1u << s.field;
   }
+  if constexpr (M == kMatchArgs) {
+    // The number a path with numeric predicates reaches.  Go holds it as a float64 f and the caller
+    // tests f >= float64(B) or f <= float64(B).  On the date form -?(0|[1-9][0-9]{0,14}) (-0 is 0, as
+    // in float64) the integer compare below is that compare for every int64 B: |v| < 10^15 < 2^53, so f
+    // is v exactly; every integer up to 2^53 is a float64 and float64() rounds monotonically, so a B
+    // with |B| <= 2^53 converts exactly, and one beyond converts to a value beyond +-2^53 of B's sign,
+    // which lies on the same side of v as B does.  Any other form (a fraction, 16 or 17 digits) is the
+    // host's: the token is JG_CL_HOST, also when a later member replaces this one.
+    if (s.nump) {
+      if ((s.st != ST_NUM_ZERO && s.st != ST_NUM_INT) || s.ndig > 15u) s.bad = 1;
+      const int64_t v = s.neg ? -(int64_t)s.val : (int64_t)s.val;
+      uint32_t m = s.nump;
+      while (m) {
+        const uint32_t k = (uint32_t)__builtin_ctz(m);
+        m &= m - 1u;
+        const int64_t b = (Q->arg >> k) & 1u ? A->bound(Q->col[k]) : Q->bound[k];
+        s.res |= ((Q->le >> k) & 1u ? v <= b : v >= b) ? 1u << k : 0u;
+      }
+      s.nump = 0;
+    }
+  }
   if constexpr (kSel<M>) sel_end(s, s.dpos, 0u);                   // dpos: the byte after the literal
   // this byte may go on to close the object around the number, itself selected by a shorter path
   if constexpr (M == kPath) sel_commit(s);
   s.st = ST_AFTER;
 }
 
-template <int M, class EX, class SL>
-JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Preds* Q = nullptr) {
+template <int M, class EX, class SL, class PQ = Preds, class AR = NoArgs>
+JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const PQ* Q = nullptr, const AR* A = nullptr) {
   (void)S;
   (void)Q;
+  (void)A;
   if (s.st >= ST_NUM_MINUS && s.st <= ST_NUM_FRAC) {
     const uint32_t d = is_digit(c);
     uint32_t nx = ST_AFTER;                           // ST_AFTER: the number ends here
@@ -689,7 +837,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Pred
       s.st = nx;
       return;
     }
-    end_number(s);                                    // ... and the byte is read as what follows a value
+    end_number(s, Q, A);                              // ... and the byte is read as what follows a value
   }
   switch (s.st) {
     case ST_STR:
@@ -724,7 +872,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Pred
               const bool is = S->len[k][d - 1u] == s.klen, last = S->ncomp[k] == d;
               slot = is && last ? k + 1u : slot;
               desc |= is && !last ? 1u << b : 0u;
-              if constexpr (M == kMatch) through |= is ? Q->all[k] : 0u;
+              if constexpr (kPred<M>) through |= is ? Q->all[k] : 0u;
             }
             (void)through;
             s.desc = desc;
@@ -735,7 +883,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Pred
               s.vtype = 0;
             }
             // a match scan: the same member takes back what an earlier one of that key gave every path through it
-            if constexpr (M == kMatch) s.res &= ~through;
+            if constexpr (kPred<M>) s.res &= ~through;
           }
         } else {
           uint32_t m = s.cand, hit = 0;
@@ -753,12 +901,14 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Pred
             s.aud_len = s.cmpf == F_AUD && !s.aud_arr ? s.dpos + 1u - s.aud_off : s.aud_len;   // aud as one string
           }
           if constexpr (kSel<M>) sel_end(s, s.dpos, s.hi);
-          if constexpr (M == kMatch) {                          // the survivors of this length are the string, or its last word
+          if constexpr (kPred<M>) {                             // the survivors of this length are the string, or its last word
             uint32_t mm = s.mcand;
             while (mm) {
               const uint32_t k = (uint32_t)__builtin_ctz(mm);
               mm &= mm - 1u;
-              s.res |= Q->len[k] == ((s.mword >> k) & 1u ? s.wpos : s.pos) ? 1u << k : 0u;
+              uint32_t l = Q->len[k];
+              if constexpr (M == kMatchArgs) l = (Q->arg >> k) & 1u ? (s.alen >> (8u * Q->col[k])) & 0xffu : l;
+              s.res |= l == ((s.mword >> k) & 1u ? s.wpos : s.pos) ? 1u << k : 0u;
             }
             s.mcand = 0;
             s.mword = 0;
@@ -790,7 +940,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Pred
           if (s.klen < 3u) s.kw = (s.kw << 8) | (c - 0x61u < 26u ? c - 0x20u : c);
           ++s.klen;
         }
-        if constexpr (M == kMatch) {
+        if constexpr (kPred<M>) {
           // Predicates whose value still equals the string (at pos) or its current word (at wpos).  A
           // space ends a word -- the word candidates of its length hold -- and arms them all again.
           const uint32_t sp = c == 0x20u ? s.mword : 0u;
@@ -798,6 +948,22 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const Pred
           while (mm) {
             const uint32_t k = (uint32_t)__builtin_ctz(mm);
             mm &= mm - 1u;
+            if constexpr (M == kMatchArgs) {
+              // An operand of the lane's own: its length from alen, its byte from the column's window,
+              // which is filled from global memory at every fourth byte while the candidate survives.
+              if ((Q->arg >> k) & 1u) {
+                const uint32_t col = Q->col[k], at = s.pos, l = (s.alen >> (8u * col)) & 0xffu;
+                uint32_t w = 0;
+                if (at < l && (at & 3u) == 0u) {
+                  w = A->word(col, at);
+                  for (uint32_t x = 0; x < JG_MAX_ARGS; ++x) s.win[x] = x == col ? w : s.win[x];
+                } else {
+                  for (uint32_t x = 0; x < JG_MAX_ARGS; ++x) w = x == col ? s.win[x] : w;
+                }
+                if (!(at < l && ((w >> (8u * (at & 3u))) & 0xffu) == c)) s.mcand &= ~(1u << k);
+                continue;
+              }
+            }
             const uint32_t at = (s.mword >> k) & 1u ? s.wpos : s.pos, l = Q->len[k];
             s.res |= l == at ? sp & (1u << k) : 0u;
             if (!(at < l && Q->pool[Q->off[k] + at] == c)) s.mcand &= ~(1u << k);
@@ -908,14 +1074,19 @@ JG_CL_HD uint8_t verdict(const ScanT<M>& s, const EX& E) {
 // The scan of one segment: claims_decide's code and, with X, the record.  The
 // state is a local of this function (handing it in by reference costs the
 // verdict-only kernel a third of its registers again).
-template <int M, class Src, class EX, class SL = Select>
+template <int M, class Src, class EX, class SL = Select, class PQ = Preds, class AR = NoArgs>
 JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* out, const SL* S = nullptr,
-                              jg_selected* sel = nullptr, const Preds* Q = nullptr, uint32_t* match = nullptr) {
-  if constexpr (M == kMatch) *match = 0;                           // JG_CL_HOST: no bit
+                              jg_selected* sel = nullptr, const PQ* Q = nullptr, uint32_t* match = nullptr,
+                              const AR* A = nullptr) {
+  (void)A;
+  if constexpr (kPred<M>) *match = 0;                              // JG_CL_HOST: no bit
   if constexpr (kRec<M>) *out = jg_claims{};                       // JG_CL_HOST: every byte zero
   if constexpr (kSel<M>) *sel = jg_selected{};
   if ((len & 3u) == 1u) return JG_CL_HOST;
   ScanT<M> s;
+  if constexpr (M == kMatchArgs) {
+    for (uint32_t x = 0; x < JG_MAX_ARGS; ++x) s.alen |= x < A->nstr() ? A->slen(x) << (8u * x) : 0u;
+  }
   const uint32_t groups = (len + 3u) >> 2;
   for (uint32_t g = 0; g < groups && !s.bad; ++g) {
     const uint32_t w = src.word(g);
@@ -929,7 +1100,7 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
     if (nb < 3u && (trip & (nb == 1u ? 0xffffu : 0xffu))) return JG_CL_HOST;
     for (uint32_t k = 0; k < nb; ++k) {
       if constexpr (kRec<M>) s.dpos = 3u * g + k;
-      step(s, (trip >> 16) & 0xffu, E, S, Q);
+      step(s, (trip >> 16) & 0xffu, E, S, Q, A);
       if constexpr (kSel<M>) sel_commit(s);
       trip <<= 8;
     }
@@ -957,7 +1128,7 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
       sel->type[k] = (uint8_t)((s.stype >> (4u * k)) & 0xfu);
     }
   }
-  if constexpr (M == kMatch) *match = s.res;
+  if constexpr (kPred<M>) *match = s.res;
   return verdict(s, E);
 }
 
@@ -1030,6 +1201,21 @@ JG_CL_HD uint8_t claims_match_each(Src& src, uint32_t len, const Profiles& T, ui
   return scan_segment<kMatch>(src, len, E, nullptr, &P, nullptr, &Q, match);
 }
 
+// claims_match_each's code and mask for a list of its ops, always, and the five
+// ops of jg_claims_match_args (include/jg.h): A is the token's own operands --
+//   uint32_t nstr()                        the string columns
+//   uint32_t slen(uint32_t c)              the length of the operand in column c
+//   uint32_t word(uint32_t c, uint32_t p)  its bytes [p, p + 4), little-endian, for p < slen(c), p % 4 == 0
+//   int64_t bound(uint32_t c)              the number in column c
+// The one difference in the code: JG_CL_HOST, mask 0, when the full path of a
+// numeric predicate reaches a number literal outside -?(0|[1-9][0-9]{0,14}).
+template <class Src, class AR>
+JG_CL_HD uint8_t claims_match_args(Src& src, uint32_t len, const Profiles& T, uint32_t p, const Paths& P,
+                                   const ArgPreds& Q, const AR& A, uint32_t* match) {
+  const ProfileRef E{T, p};
+  return scan_segment<kMatchArgs>(src, len, E, nullptr, &P, nullptr, &Q, match, &A);
+}
+
 }  // namespace jgclaims
 
 #if defined(__HIPCC__)
@@ -1042,6 +1228,9 @@ JG_CL_HD uint8_t claims_match_each(Src& src, uint32_t len, const Profiles& T, ui
 //   select, sel_out  k_claims_select[_each]: and sel_out[i] = the members `select` names (with vals_out)
 //   paths, sel_out   k_claims_paths_each: `paths` in the place of the names (with table and vals_out)
 //   paths, preds, match_out   k_claims_match_each: match_out[i] = the predicates that hold (with table; no record)
+//   paths, apreds, match_out  k_claims_match_args: the same with apreds in the place of preds, and job i's operands:
+//                             arg_str[i * nstr + c] (a span of arg_bytes, which has ARENA_SLACK behind it) and
+//                             arg_num[i * nnum + c]
 struct ClaimsLaunch {
   const uint8_t* arena = nullptr;
   const jg_cjob* jobs = nullptr;
@@ -1051,6 +1240,11 @@ struct ClaimsLaunch {
   const jgclaims::Select* select = nullptr;
   const jgclaims::Paths* paths = nullptr;
   const jgclaims::Preds* preds = nullptr;
+  const jgclaims::ArgPreds* apreds = nullptr;
+  const uint8_t* arg_bytes = nullptr;
+  const jg_sarg* arg_str = nullptr;
+  const int64_t* arg_num = nullptr;
+  uint32_t nstr = 0, nnum = 0;
   uint8_t* code_out = nullptr;
   jg_claims* vals_out = nullptr;
   jg_selected* sel_out = nullptr;

@@ -26,6 +26,7 @@ HTTP is the caller's: NewJSONWebKeySet / NewOIDCDiscoveryKeySet take a
 `fetch(url, ca_pem) -> {"status", "body", "content_type", "max_age"}` callable
 standing in for the reference's net/http client (raise for a transport error).
 """
+import array
 import dataclasses
 import datetime
 from typing import Callable, List, Optional, Sequence
@@ -229,6 +230,81 @@ def _requires_of(requires):
         if not isinstance(r, Require):
             raise TypeError("requires: elements are built by Equals, HasWord, HasElement or Present")
         out.append((list(r[0]), r[1], r[2]))
+    return out
+
+
+class ArgRequire(tuple):
+    """A requirement whose other side is the token's own operand, or a number: an
+    element of the `requires` of MatchBatchArgs / MatchBlobArgs and their *Each
+    forms, beside Require's: (path, op, "", bound, column).  Built by EqualsEach,
+    AtLeast, AtMost, AtLeastEach and AtMostEach."""
+    EQUALS_ARG, NUM_GE, NUM_LE, NUM_GE_ARG, NUM_LE_ARG = 5, 6, 7, 8, 9     # jg_pred_op (include/jg.h)
+    _NAMES = {5: "EqualsEach", 6: "AtLeast", 7: "AtMost", 8: "AtLeastEach", 9: "AtMostEach"}
+
+    def __new__(cls, path_or_name, op, bound=0, column=0):
+        path = path_or_name if isinstance(path_or_name, Path) else Path(path_or_name)
+        for what, v, lo, hi in (("bound", bound, -(1 << 63), (1 << 63) - 1), ("column", column, 0, (1 << 32) - 1)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError("ArgRequire: the %s is an int" % what)
+            if not lo <= v <= hi:
+                raise ValueError("ArgRequire: the %s does not fit" % what)
+        return super().__new__(cls, (path, int(op), "", bound, column))
+
+    def __repr__(self):
+        return "%s(%r, %r)" % (self._NAMES.get(self[1], "ArgRequire"), self[0],
+                               self[3] if self[1] in (self.NUM_GE, self.NUM_LE) else self[4])
+
+
+def EqualsEach(path_or_name, column: int) -> ArgRequire:
+    """The claim is a string equal to the token's own entry in string column `column` ("" allowed)."""
+    return ArgRequire(path_or_name, ArgRequire.EQUALS_ARG, column=column)
+
+
+def AtLeast(path_or_name, n: int) -> ArgRequire:
+    """The claim is a number f with f >= float64(n), as Go compares a claims map's float64."""
+    return ArgRequire(path_or_name, ArgRequire.NUM_GE, bound=n)
+
+
+def AtMost(path_or_name, n: int) -> ArgRequire:
+    """The claim is a number f with f <= float64(n)."""
+    return ArgRequire(path_or_name, ArgRequire.NUM_LE, bound=n)
+
+
+def AtLeastEach(path_or_name, column: int) -> ArgRequire:
+    """AtLeast with the token's own entry in number column `column` as n."""
+    return ArgRequire(path_or_name, ArgRequire.NUM_GE_ARG, column=column)
+
+
+def AtMostEach(path_or_name, column: int) -> ArgRequire:
+    """AtMost with the token's own entry in number column `column` as n."""
+    return ArgRequire(path_or_name, ArgRequire.NUM_LE_ARG, column=column)
+
+
+def _arg_requires_of(requires):
+    out = []
+    for r in requires:
+        if isinstance(r, Require):
+            out.append((list(r[0]), r[1], r[2], 0, 0))
+        elif isinstance(r, ArgRequire):
+            out.append((list(r[0]), r[1], r[2], r[3], r[4]))
+        else:
+            raise TypeError("requires: elements are built by Equals, HasWord, HasElement, Present, EqualsEach, "
+                            "AtLeast, AtMost, AtLeastEach or AtMostEach")
+    return out
+
+
+def _num_columns(nums):
+    """Number columns as buffers of int64: a buffer (array('q'), a numpy int64 array) as it is, a sequence of int packed"""
+    out = []
+    for col in nums:
+        try:
+            memoryview(col)
+        except TypeError:
+            try:
+                col = array.array("q", col)
+            except OverflowError:
+                raise ValueError("a number column holds a value outside int64") from None
+        out.append(col)
     return out
 
 
@@ -464,6 +540,63 @@ class Validator:
         return cols
 
 
+    # ---- ... with an operand per token, and numeric tests
+    def MatchBatchArgs(self, tokens: Sequence, requires: Sequence, strs: Sequence = (), nums: Sequence = (),
+                       expected: Expected = None, stats: dict = None):
+        """MatchBatch for the checks whose other side differs from token to token: the
+        nonce of that request, auth_time under its max_age, sub against the session's
+        subject.  `requires` may also hold EqualsEach(path, c) -- the claim equals
+        strs[c][i] for tokens[i] --, AtLeast / AtMost(path, n) -- the claim is a
+        number >= / <= n, as Go compares the claims map's float64 -- and AtLeastEach /
+        AtMostEach(path, c) with nums[c][i] as n.  `strs`: columns of str, one entry
+        per token; `nums`: columns of int64, each a buffer (array('q'), a numpy int64
+        array) or a sequence of int.  Rows as MatchBatch's.  The scan decides a
+        numeric requirement on an integer literal of at most 15 digits; a token whose
+        number is written otherwise, or whose own operand the scan does not take
+        (over 64 bytes, or not printable ASCII without quote and backslash) is
+        answered from the host path, as is every token of a list over the scan's caps
+        (MatchBatch's, or more than 4 columns of a kind).  A column whose length is
+        not len(tokens), a column index without a column, more than 16 requirements,
+        a NUL in an operand: ValueError."""
+        rows, scanned, host = self._impl.match_batch_args(list(tokens), _arg_requires_of(requires),
+                                                          [list(c) for c in strs], _num_columns(nums),
+                                                          (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return [tuple(r) for r in rows]
+
+    def MatchBlobArgs(self, blob: bytes, requires: Sequence, strs: Sequence = (), nums: Sequence = (),
+                      expected: Expected = None, stats: dict = None) -> dict:
+        """MatchBatchArgs' throughput form: newline-separated tokens and, per string
+        column, newline-separated operands (bytes; an empty line is the operand "")
+        -> MatchBlob's columns."""
+        cols, scanned, host = self._impl.match_blob_args(blob, _arg_requires_of(requires), [bytes(c) for c in strs],
+                                                         _num_columns(nums), (expected or Expected())._native())
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
+    def MatchBatchArgsEach(self, tokens: Sequence, requires: Sequence, expected: Sequence[Expected],
+                           which: Sequence[int], strs: Sequence = (), nums: Sequence = (), stats: dict = None):
+        """MatchBatchArgs with expected[which[i]] for tokens[i]."""
+        rows, scanned, host = self._impl.match_batch_args_each(list(tokens), _arg_requires_of(requires),
+                                                               [list(c) for c in strs], _num_columns(nums),
+                                                               self._natives(expected), list(which))
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return [tuple(r) for r in rows]
+
+    def MatchBlobArgsEach(self, blob: bytes, requires: Sequence, expected: Sequence[Expected], which,
+                          strs: Sequence = (), nums: Sequence = (), stats: dict = None) -> dict:
+        """MatchBlobArgs with expected[which[i]] for token i; `which` as in CheckBlobEach."""
+        cols, scanned, host = self._impl.match_blob_args_each(blob, _arg_requires_of(requires),
+                                                              [bytes(c) for c in strs], _num_columns(nums),
+                                                              self._natives(expected), which)
+        if stats is not None:
+            stats.update(scanned=scanned, host=host)
+        return cols
+
+
 def NewValidator(keyset: Optional[KeySet]):
     if keyset is None:
         return None, "keySet must not be nil"
@@ -473,4 +606,5 @@ def NewValidator(keyset: Optional[KeySet]):
 __all__ = ["RS256", "RS384", "RS512", "ES256", "ES384", "ES512", "PS256", "PS384", "PS512", "EdDSA",
            "DefaultLeewaySeconds", "PublicKey", "SupportedSigningAlgorithm", "ParsePublicKeyPEM", "KeySet",
            "NewStaticKeySet", "NewJSONWebKeySet", "NewOIDCDiscoveryKeySet", "Expected", "Path", "Validator",
-           "NewValidator", "Require", "Equals", "HasWord", "HasElement", "Present"]
+           "NewValidator", "Require", "Equals", "HasWord", "HasElement", "Present", "ArgRequire", "EqualsEach",
+           "AtLeast", "AtMost", "AtLeastEach", "AtMostEach"]

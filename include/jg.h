@@ -609,7 +609,11 @@ int jg_claims_paths(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
  * NULL with njobs > 0. */
 #define JG_MAX_PRED 16
 #define JG_PRED_VALUE_MAX 64
-enum jg_pred_op { JG_PRED_EQUALS = 1, JG_PRED_HAS_WORD = 2, JG_PRED_HAS_ELEMENT = 3, JG_PRED_PRESENT = 4 };
+enum jg_pred_op {
+  JG_PRED_EQUALS = 1, JG_PRED_HAS_WORD = 2, JG_PRED_HAS_ELEMENT = 3, JG_PRED_PRESENT = 4,
+  /* jg_claims_match_args only; jg_claims_match refuses them as unknown */
+  JG_PRED_EQUALS_ARG = 5, JG_PRED_NUM_GE = 6, JG_PRED_NUM_LE = 7, JG_PRED_NUM_GE_ARG = 8, JG_PRED_NUM_LE_ARG = 9
+};
 typedef struct jg_preds {
   const uint8_t* values;                     /* the predicates' values, back to back */
   uint32_t n;                                /* 0..JG_MAX_PRED */
@@ -621,6 +625,60 @@ int jg_claims_match(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                     const jg_cjob* jobs, size_t njobs,
                     const jg_expect* expects, uint32_t nexpect, const jg_paths* paths, const jg_preds* preds,
                     uint8_t* code_out, uint32_t* match_out);
+
+/* ---- predicates with an operand per token, and numeric tests ----
+ * jg_claims_match for the checks whose other side differs from token to token
+ * (the nonce of that request, oidc/provider.go:447; auth_time under that
+ * request's max_age, :499-508; sub against the session's subject; cnf.jkt
+ * against the thumbprint of the request's DPoP key): the same jobs, profiles,
+ * paths, preds, code_out and match_out, and `args`, the operands of every job:
+ * nstr string columns (job i's operand in column c is bytes[off, off + len) of
+ * str[i * nstr + c]) and nnum columns of int64 (num[i * nnum + c]).  Five more
+ * ops, with v the value the walk reaches as for the other four:
+ *  - JG_PRED_EQUALS_ARG: v is a string whose bytes equal job i's operand in
+ *    string column c.  value_len is 1 and the value byte is c (< nstr).  An
+ *    operand of length 0 means "".  What JG_PRED_EQUALS says about bytes >= 0x80
+ *    holds here too;
+ *  - JG_PRED_NUM_GE / JG_PRED_NUM_LE: v is a JSON number f with f >= float64(B)
+ *    (f <= float64(B)): what `f, ok := claims[..].(float64); ok && f >=
+ *    float64(B)` gives in Go.  value_len is 8, the value B as a little-endian
+ *    int64;
+ *  - JG_PRED_NUM_GE_ARG / JG_PRED_NUM_LE_ARG: the same with B = num[i * nnum +
+ *    c]; value_len is 1 and the value byte is c (< nnum).
+ * Operand bytes follow a value's rules (0x20..0x7e without " and \), at most
+ * JG_PRED_VALUE_MAX each; every operand of every job is checked before the
+ * launch.
+ * The device decides a numeric predicate only on a literal of the date form
+ * -?(0|[1-9][0-9]{0,14}) (-0 counts as 0), where the integer compare is the
+ * float64 compare for every int64 B.  Whenever the full path of a numeric
+ * predicate reaches a number of any other accepted form (a fraction, 16 or 17
+ * digits) -- also in a member that a later duplicate key replaces -- the token is
+ * JG_CL_HOST, mask 0.  That is the one exception to "predicates never change a
+ * code", and only a list with a numeric op can cause it; for every other token
+ * code_out[i] is jg_claims_each's, byte for byte.  A string, array, literal or
+ * object under a numeric predicate is bit 0, not HOST.
+ * With no op >= 5 in the list the outputs are jg_claims_match's, byte for byte.
+ * Everything else is jg_claims_match's (three more kept buffers: the operand
+ * bytes, the span table and the numbers, uploaded per call: 8 bytes plus the
+ * operand per token and string column, 8 bytes per token and number column).
+ * -1: everything jg_claims_match refuses (its unknown ops are here those outside
+ * 1..9); nstr or nnum over JG_MAX_ARGS; a column index past its count; a
+ * value_len that is not the op's; two predicates with the same path, op and
+ * column (or bound); args NULL, or bytes / str / num NULL where bytes_len / nstr
+ * / nnum is not 0, with njobs > 0; and, naming the job: an operand byte a value
+ * may not hold, a len over JG_PRED_VALUE_MAX, a span past bytes_len. */
+#define JG_MAX_ARGS 4
+typedef struct jg_sarg { uint32_t off, len; } jg_sarg;   /* bytes[off, off+len), len 0..JG_PRED_VALUE_MAX */
+typedef struct jg_args {
+  const uint8_t* bytes; size_t bytes_len;    /* the string operands */
+  const jg_sarg* str;                        /* njobs x nstr, job-major */
+  const int64_t* num;                        /* njobs x nnum, job-major */
+  uint32_t nstr, nnum;                       /* 0..JG_MAX_ARGS each */
+} jg_args;
+int jg_claims_match_args(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                         const jg_cjob* jobs, size_t njobs,
+                         const jg_expect* expects, uint32_t nexpect, const jg_paths* paths, const jg_preds* preds,
+                         const jg_args* args, uint8_t* code_out, uint32_t* match_out);
 
 /* Library build information (gfx target, version). */
 const char* jg_version(void);

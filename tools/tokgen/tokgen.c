@@ -7,7 +7,7 @@
  *
  * Token i uses key i % nkeys; header {"alg":ALG,"kid":"kid-KK","typ":"JWT"},
  * payload shaped like cap's testJWTClaims (jwt/keyset_test.go:666-677) with
- * jti = i (TOKGEN_PAD / TOKGEN_EXTRA add members).  One token per line.  PS* use salt length = hash length (go-jose).
+ * jti = i (TOKGEN_PAD / TOKGEN_EXTRA / TOKGEN_OIDC add members).  One token per line.  PS* use salt length = hash length (go-jose).
  * RS*, ES* and EdDSA tokens are the same bytes on every run (ES* nonces are
  * derived, see es_sign); PS* salts are random.
  */
@@ -113,13 +113,18 @@ static void* worker(void* arg) {
    * (e.g. "roles":["admin"],"scope":"read write", -- with the trailing comma) */
   const char* extra = getenv("TOKGEN_EXTRA");
   if (!extra) extra = "";
+  /* TOKGEN_OIDC=1: token i also carries "nonce":"n-<i as 20 hex digits>" (22 bytes, its own) and
+   * "auth_time":1611699344 - i % 3600, in front of TOKGEN_EXTRA's members */
+  const char* oe = getenv("TOKGEN_OIDC");
+  const int oidc = oe && atol(oe) != 0;
+  char oidcv[96] = "";
   /* TOKGEN_TENANTS=P: token i belongs to tenant i % P, with an issuer and an
    * audience of its own of the default ones' lengths ("https://t07.example/",
    * "c07.example.com"); unset or 0: the default issuer and audience */
   const char* te = getenv("TOKGEN_TENANTS");
   const long tenants = te ? atol(te) : 0;
   char iss[64] = "https://example.com/", aud[64] = "www.example.com";
-  const size_t cap = 512 + padn + strlen(extra);
+  const size_t cap = 512 + sizeof oidcv + padn + strlen(extra);
   char hdr[256], hb[512], sb[1500];
   char* pay = malloc(cap);
   char* pb = malloc(2 * cap + 8);
@@ -135,16 +140,17 @@ static void* worker(void* arg) {
       snprintf(aud, sizeof aud, "c%02ld.example.com", i % tenants);
     }
     snprintf(hdr, sizeof hdr, "{\"alg\":\"%s\",\"kid\":\"kid-%02d\",\"typ\":\"JWT\"}", j->alg, j->kid_base + k);
+    if (oidc) snprintf(oidcv, sizeof oidcv, "\"nonce\":\"n-%020lx\",\"auth_time\":%ld,", i, 1611699344L - i % 3600);
     if (padn)
       snprintf(pay, cap,
                "{\"aud\":[\"%s\"],\"exp\":1611699944,\"iat\":1611699344,"
                "\"iss\":\"%s\",\"jti\":\"%ld\",\"nbf\":1611699344,\"pad\":\"%s\","
-               "%s\"sub\":\"alice@example.com\"}", aud, iss, i, padv, extra);
+               "%s%s\"sub\":\"alice@example.com\"}", aud, iss, i, padv, oidcv, extra);
     else
       snprintf(pay, cap,
                "{\"aud\":[\"%s\"],\"exp\":1611699944,\"iat\":1611699344,"
-               "\"iss\":\"%s\",\"jti\":\"%ld\",\"nbf\":1611699344,%s\"sub\":\"alice@example.com\"}",
-               aud, iss, i, extra);
+               "\"iss\":\"%s\",\"jti\":\"%ld\",\"nbf\":1611699344,%s%s\"sub\":\"alice@example.com\"}",
+               aud, iss, i, oidcv, extra);
     size_t hl = b64url((const unsigned char*)hdr, strlen(hdr), hb);
     size_t pl = b64url((const unsigned char*)pay, strlen(pay), pb);
     char* si = malloc(hl + pl + 2);
