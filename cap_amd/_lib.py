@@ -28,7 +28,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest", "jg_debug_table_read",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
            "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
-           "jg_claims_paths", "jg_claims_match", "jg_claims_match_args"]
+           "jg_claims_paths", "jg_claims_match", "jg_claims_match_args", "jg_claims_match_hash"]
 
 
 class JgKey(ctypes.Structure):
@@ -125,6 +125,10 @@ PRED_EQUALS, PRED_HAS_WORD, PRED_HAS_ELEMENT, PRED_PRESENT = 1, 2, 3, 4
 # ... and those only jg_claims_match_args takes: the value is a column index (one byte) or an int64 bound
 PRED_EQUALS_ARG, PRED_NUM_GE, PRED_NUM_LE, PRED_NUM_GE_ARG, PRED_NUM_LE_ARG = 5, 6, 7, 8, 9
 MAX_ARGS = 4                                 # JG_MAX_ARGS
+# ... and those only jg_claims_match_hash takes: the value is a hash column index (one byte), or nothing
+PRED_EQUALS_HASH, PRED_IS_STRING = 10, 11
+MAX_HASH_ARGS, HASH_SRC_MAX = 2, 8192        # JG_MAX_HASH_ARGS, JG_HASH_SRC_MAX
+SHA256, SHA384, SHA512 = 1, 2, 3             # jg_hash_fam; 0 in a jg_hsrc: the job has no value
 
 
 class JgPreds(ctypes.Structure):
@@ -145,6 +149,54 @@ class JgArgs(ctypes.Structure):
 
 
 assert ctypes.sizeof(JgSArg) == 8
+
+
+class JgHSrc(ctypes.Structure):
+    """jg_hsrc: one value to hash, a span of jg_hargs.bytes and its family"""
+    _fields_ = [("off", ctypes.c_uint32), ("len", ctypes.c_uint32), ("fam", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 3)]
+
+
+class JgHArgs(ctypes.Structure):
+    """jg_hargs: the per-job hash sources of jg_claims_match_hash"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("bytes_len", ctypes.c_size_t), ("src", ctypes.c_void_p),
+                ("nhash", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(JgHSrc) == 12 and ctypes.sizeof(JgHArgs) == 32
+
+
+def pack_hargs(cols=(), lead=0):
+    """Hash columns -> the dict Context.claims_match_hash takes.  `cols`: hash
+    columns, each one (value bytes, fam) per job, or None for "no value" (fam 0,
+    an empty span).  The values are packed job-major, back to back after `lead`
+    filler bytes, so the last one ends at the last byte.  {"bytes", "src": a row of
+    (off, len, fam) per job, "nhash"}: a test may edit any of it."""
+    n = len(cols[0]) if cols else 0
+    blob, src = bytearray(b"#" * lead), []
+    for i in range(n):
+        row = []
+        for col in cols:
+            v, fam = col[i] if col[i] is not None else (b"", 0)
+            row.append((len(blob), len(v), fam))
+            blob += bytes(v)
+        src.append(row)
+    return {"bytes": bytes(blob), "src": src, "nhash": len(cols)}
+
+
+def _jg_hargs(a, null=()):
+    """pack_hargs' dict -> (JgHArgs, the buffers to keep alive)"""
+    blob = a["bytes"]
+    keep = ctypes.create_string_buffer(blob, max(1, len(blob)))
+    flat = [x for row in a["src"] for x in row]
+    sp = (JgHSrc * max(1, len(flat)))()
+    for t, (off, ln, fam) in zip(sp, flat):
+        t.off, t.len, t.fam = off, ln, fam
+    g = JgHArgs()
+    g.bytes = None if "hbytes" in null else ctypes.cast(keep, ctypes.c_void_p)
+    g.bytes_len = a.get("bytes_len", len(blob))
+    g.src = None if "hsrc" in null else ctypes.cast(sp, ctypes.c_void_p)
+    g.nhash = a["nhash"]
+    return g, (keep, sp)
 
 
 def pack_args(strs=(), nums=(), lead=0):
@@ -327,6 +379,9 @@ def lib():
         L.jg_claims_match_args.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
                                            ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds),
                                            ctypes.POINTER(JgArgs), vp, vp]
+        L.jg_claims_match_hash.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                           ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds),
+                                           ctypes.POINTER(JgArgs), ctypes.POINTER(JgHArgs), vp, vp]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -659,6 +714,32 @@ class Context:
                           None if "paths" in null else ctypes.byref(ps),
                           None if "preds" in null else ctypes.byref(qs),
                           None if "args" in null else ctypes.byref(ga),
+                          None if "codes" in null else out,
+                          None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
+        return out.raw[:n], list(masks[:n])
+
+    def claims_match_hash(self, arena_bytes, jobs, expects, paths, preds, args=None, hargs=None, nexpect=None, null=()):
+        """jg_claims_match_hash: claims_match_args with hash columns.  `preds` may
+        also hold PRED_EQUALS_HASH (the value is one byte, the hash column) and
+        PRED_IS_STRING (no value); `args`: pack_args' dict, or None for NULL (no
+        plain columns); `hargs`: pack_hargs' dict, or None for NULL (no hash
+        column) -> (codes: bytes, masks: list of int), both poisoned with 0xee
+        before the call.  `null` names arguments ("paths", "preds", "codes",
+        "masks") or members of the operands ("bytes", "str", "num", "hbytes",
+        "hsrc") to pass as NULL."""
+        n = len(jobs)
+        es, _keep = _jg_expects(expects)
+        ps, _nkeep = _jg_paths(paths)
+        qs, _vkeep = _jg_preds(preds)
+        ga, _akeep = _jg_args(args, null) if args is not None else (None, None)
+        gh, _hkeep = _jg_hargs(hargs, null) if hargs is not None else (None, None)
+        out, masks = _poisoned(ctypes.c_char, n), _poisoned(ctypes.c_uint32, n)
+        self._claims_call("jg_claims_match_hash", arena_bytes, _cjobs(jobs), n, es,
+                          len(expects) if nexpect is None else nexpect,
+                          None if "paths" in null else ctypes.byref(ps),
+                          None if "preds" in null else ctypes.byref(qs),
+                          None if ga is None else ctypes.byref(ga),
+                          None if gh is None else ctypes.byref(gh),
                           None if "codes" in null else out,
                           None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
         return out.raw[:n], list(masks[:n])

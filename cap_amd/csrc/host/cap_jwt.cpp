@@ -2007,7 +2007,8 @@ struct MatchPlan {
   // jg_args (job-major spans into `abytes`, numbers in `anums`); host_only[i]: token i has a string operand the
   // scan refuses, so it is not scanned and its spans are empty.
   MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vector<std::vector<std::string_view>>& strs,
-            const std::vector<const int64_t*>& nums, bool with_args = true);
+            const std::vector<const int64_t*>& nums, bool with_args = true,
+            const std::vector<HashColumn>* hashes = nullptr);
   bool with_args = false;
   const std::vector<std::vector<std::string_view>>* strs = nullptr;
   const std::vector<const int64_t*>* nums = nullptr;
@@ -2016,6 +2017,17 @@ struct MatchPlan {
   std::vector<int64_t> anums;
   std::vector<uint8_t> host_only;
   jg_args args{};
+  // The hash columns (jg_claims_match_hash), with_hash: the call has one, or a HashOfArg or IsString.  The
+  // values travel as a jg_hargs (job-major spans into `hbytes`); a token whose value is over JG_HASH_SRC_MAX is
+  // host_only.  The family of a span is its token's alg's, known once the batch is parsed: set_families().
+  bool with_hash = false;
+  bool hash_reqs = false;                             // a HashOfArg among the requirements
+  const std::vector<HashColumn>* hashes = nullptr;
+  std::string hbytes;
+  mutable std::vector<jg_hsrc> hsrc;
+  jg_hargs hargs{};
+  // host path: hosted[i * nhash + c] is what token i's claim must equal under hash column c, "" for none
+  mutable std::vector<std::string> hosted;
   // token i's operands for the host path
   uint32_t host_bits(const json::Value& claims, size_t i) const;
   // the caller's mask from the scan's
@@ -2026,6 +2038,8 @@ struct MatchPlan {
     return out;
   }
 };
+
+int hash_fam_of_alg(int alg);                        // the SHA-2 of a token's hash claims, below
 
 // One Expected as the scan takes it (include/jg.h jg_expect) and the clock its
 // tokens are held to.  scannable == false: one the ABI does not take (more than
@@ -2165,7 +2179,20 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     try {
       const jg_expect& ex = exs[0];
       if constexpr (M == kMatchMode) {
-        if (match->with_args)
+        if (match->with_hash) {
+          // a value is hashed with the SHA-2 of its token's alg; a token that is not scanned has no value here
+          const size_t nh = match->hargs.nhash;
+          if (nh)
+            parallel_for(n, th, [&](size_t lo, size_t hi) {
+              for (size_t i = lo; i < hi; ++i)
+                for (size_t c = 0; c < nh; ++c) {
+                  jg_hsrc& s = match->hsrc[i * nh + c];
+                  if (s.fam) s.fam = (uint8_t)(jobs[i].len ? hash_fam_of_alg(V.toks[i].alg) : 0);
+                }
+            });
+          eng.claims_match_hash(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
+                                &match->preds, &match->args, &match->hargs, code, masks, true);
+        } else if (match->with_args)
           eng.claims_match_args(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
                                 &match->preds, &match->args, code, masks, true);
         else
@@ -2194,6 +2221,50 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   PhaseTimer pt("check");
   const Chunks ch = make_chunks(n, th);
   std::vector<size_t> n_scan(ch.count(), 0), n_host(ch.count(), 0);
+  // The host path of HashOfArg: one jg_hash_batch call over the values of just the tokens that take it.
+  bool hash_failed = false;
+  std::string hash_err;
+  std::vector<uint8_t> needs_hash;
+  if constexpr (M == kMatchMode) {
+    if (match->with_hash && match->hash_reqs) {
+      const size_t nh = match->hashes->size();
+      std::vector<jg_hjob> hjobs;
+      std::vector<size_t> at;                           // i * nh + c of each job
+      std::string harena;
+      for (size_t i = 0; i < n; ++i) {
+        const Tok& t = V->toks[i];
+        if (!(t.parsed && !V->failed[i] && V->any[i]) || code[i] != JG_CL_HOST) continue;
+        if (scan_failed && have_jobs && jobs[i].len) continue;
+        const int fam = hash_fam_of_alg(t.alg);
+        for (size_t c = 0; c < nh && fam; ++c) {
+          const auto& v = (*match->hashes)[c][i];
+          if (!v) continue;
+          jg_hjob j{};
+          j.off = harena.size();
+          j.len = (uint32_t)v->size();
+          j.fam = (uint8_t)fam;
+          hjobs.push_back(j);
+          at.push_back(i * nh + c);
+          harena.append(*v);
+        }
+      }
+      if (!hjobs.empty()) {
+        match->hosted.assign(n * nh, std::string());
+        std::vector<uint8_t> dig(64 * hjobs.size());
+        try {
+          eng.hash((const uint8_t*)harena.data(), harena.size(), hjobs.data(), hjobs.size(), dig.data());
+          for (size_t k = 0; k < hjobs.size(); ++k) match->hosted[at[k]] = hash_claim_value(&dig[64 * k], hjobs[k].fam);
+        } catch (const DeviceError& e) {
+          // as a failed scan: the tokens that needed the device get its error, and the context is recreated
+          hash_failed = true;
+          hash_err = std::string("capjwt: claims scan unavailable: ") + e.what();
+          needs_hash.assign(n, 0);
+          for (size_t k : at) needs_hash[k / nh] = 1;
+          (void)eng.recover(eng.errors());
+        }
+      }
+    }
+  }
   const Expected* const one = exps;                   // Each = false: the one Expected and its clock
   const int64_t one_now = Each ? 0 : prof[0].now;
   run_chunks(ch, [&](size_t c, size_t lo, size_t hi) {
@@ -2214,6 +2285,10 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
       }
       if (code[i] == JG_CL_HOST) {
         ++nh;
+        if (hash_failed && needs_hash[i]) {
+          reject(c, i, std::string(hash_err));
+          continue;
+        }
         Result r;
         ks_->finish(*V, i, r);
         if (!r.ok) {
@@ -2814,14 +2889,14 @@ void Engine::hash(const uint8_t* arena, size_t arena_len, const void* jobs, size
 // ---- MatchBatch: predicates on claims, answered by the scan ----
 namespace {
 // what MatchBatch refuses whatever path decides the tokens
-void check_requires(const std::vector<Require>& reqs, bool with_args = false) {
+void check_requires(const std::vector<Require>& reqs, Require::Op max_op = Require::Present) {
   if (reqs.size() > kMaxRequires) throw std::invalid_argument("capjwt: more than 16 requirements: the mask has no bit for them");
   for (const Require& r : reqs) {
     if (r.path.empty()) throw std::invalid_argument("capjwt: a claim path has no component");
     for (const std::string& comp : r.path)
       if (comp.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim path holds a NUL byte");
     if (r.value.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a required value holds a NUL byte");
-    if (r.op < Require::Equals || r.op > (with_args ? Require::AtMostArg : Require::Present))
+    if (r.op < Require::Equals || r.op > max_op)
       throw std::invalid_argument("capjwt: an unknown requirement op");
   }
 }
@@ -2830,8 +2905,9 @@ bool scan_byte_ok(unsigned char c) { return c >= 0x20 && c <= 0x7e && c != '"' &
 // how a requirement's other side travels in jg_preds::values: the text, the column (one byte), or the bound
 std::string pred_value(const Require& r) {
   switch (r.op) {
-    case Require::Present: return std::string();
-    case Require::EqualsArg: case Require::AtLeastArg: case Require::AtMostArg: return std::string(1, (char)r.column);
+    case Require::Present: case Require::IsString: return std::string();
+    case Require::EqualsArg: case Require::AtLeastArg: case Require::AtMostArg: case Require::HashOfArg:
+      return std::string(1, (char)r.column);
     case Require::AtLeast: case Require::AtMost: {
       std::string v(8, '\0');
       for (int b = 0; b < 8; ++b) v[b] = (char)((uint64_t)r.bound >> (8 * b));
@@ -2846,10 +2922,21 @@ const std::vector<const int64_t*> kNoNums;
 MatchPlan::MatchPlan(const std::vector<Require>& reqs) : MatchPlan(reqs, 0, kNoStrs, kNoNums, false) {}
 
 MatchPlan::MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vector<std::vector<std::string_view>>& strs_,
-                     const std::vector<const int64_t*>& nums_, bool with_args_)
-    : reqs(reqs), bit(reqs.size(), -1), with_args(with_args_), strs(&strs_), nums(&nums_) {
+                     const std::vector<const int64_t*>& nums_, bool with_args_, const std::vector<HashColumn>* hashes_)
+    : reqs(reqs), bit(reqs.size(), -1), with_args(with_args_), strs(&strs_), nums(&nums_), hashes(hashes_) {
   const bool plain = !with_args;                      // MatchBatch's rules: ops 1..4 only
-  check_requires(reqs, !plain);
+  check_requires(reqs, plain ? Require::Present : Require::IsString);
+  const size_t nh = hashes ? hashes->size() : 0;
+  with_hash = nh > 0;
+  for (const Require& r : reqs) {
+    if (r.op == Require::HashOfArg && r.column >= nh)
+      throw std::invalid_argument("capjwt: a requirement names a hash column that was not given");
+    with_hash = with_hash || r.op >= Require::HashOfArg;
+    hash_reqs = hash_reqs || r.op == Require::HashOfArg;
+  }
+  for (size_t c = 0; c < nh; ++c)
+    if ((*hashes)[c].size() != n) throw std::invalid_argument("capjwt: a hash column does not hold one entry per token");
+  if (nh > JG_MAX_HASH_ARGS || strs_.size() + nh > JG_MAX_ARGS) usable = false;
   for (const Require& r : reqs) {
     if (r.op == Require::EqualsArg && r.column >= strs_.size())
       throw std::invalid_argument("capjwt: a requirement names a string column that was not given");
@@ -2970,13 +3057,61 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vect
   args.num = anums.data();
   args.nstr = (uint32_t)ns;
   args.nnum = (uint32_t)nn;
+  if (!nh) return;
+  // the values to hash, job-major and back to back; the families are set when the tokens' algs are known
+  hsrc.assign(n * nh, jg_hsrc{});
+  size_t total = 0;
+  for (size_t i = 0; i < n; ++i)
+    for (size_t c = 0; c < nh; ++c) {
+      const auto& v = (*hashes)[c][i];
+      if (v && v->size() > JG_HASH_SRC_MAX) host_only[i] = 1;
+    }
+  for (size_t i = 0; i < n; ++i)
+    for (size_t c = 0; c < nh && !host_only[i]; ++c)
+      if ((*hashes)[c][i]) total += (*hashes)[c][i]->size();
+  if (total > 0xffffffffu - 4096) {
+    usable = false;
+    return;
+  }
+  hbytes.resize(total);
+  size_t o = 0;
+  for (size_t i = 0; i < n; ++i)
+    for (size_t c = 0; c < nh && !host_only[i]; ++c) {
+      const auto& v = (*hashes)[c][i];
+      if (!v) continue;
+      hsrc[i * nh + c].off = (uint32_t)o;
+      hsrc[i * nh + c].len = (uint32_t)v->size();
+      hsrc[i * nh + c].fam = 0xff;                      // a value: set_families() puts the token's family here
+      if (!v->empty()) std::memcpy(&hbytes[o], v->data(), v->size());
+      o += v->size();
+    }
+  hargs.bytes = (const uint8_t*)hbytes.data();
+  hargs.bytes_len = hbytes.size();
+  hargs.src = hsrc.data();
+  hargs.nhash = (uint32_t)nh;
+}
+
+// the SHA-2 of an id_token's hash claims by its alg (oidc/id_token.go:106-119); 0: none (EdDSA, no alg)
+int hash_fam_of_alg(int alg) {
+  switch (alg) {
+    case JG_RS256: case JG_ES256: case JG_PS256: return JG_SHA256;
+    case JG_RS384: case JG_ES384: case JG_PS384: return JG_SHA384;
+    case JG_RS512: case JG_ES512: case JG_PS512: return JG_SHA512;
+    default: return 0;
+  }
 }
 }  // namespace
 
+std::string hash_claim_value(const uint8_t* digest, int fam) {
+  const size_t half = (fam == JG_SHA256 ? 32 : fam == JG_SHA384 ? 48 : 64) / 2;
+  return b64url_encode(std::string_view((const char*)digest, half));
+}
+
 namespace {
 // the requirements on a claims map; strs / nums: one token's operands, for the ops that take one
+// hashed: what the token's claim must equal under each hash column, "" for none
 uint32_t requires_on(const json::Value& all_claims, const std::vector<Require>& reqs, const std::string_view* strs,
-                     const int64_t* nums) {
+                     const int64_t* nums, const std::string* hashed = nullptr) {
   uint32_t bits = 0;
   for (size_t k = 0; k < reqs.size(); ++k) {
     const Require& r = reqs[k];
@@ -3016,6 +3151,10 @@ uint32_t requires_on(const json::Value& all_claims, const std::vector<Require>& 
       case Require::AtMost: hit = v->kind == json::Value::Number && v->num <= (double)r.bound; break;
       case Require::AtLeastArg: hit = v->kind == json::Value::Number && v->num >= (double)nums[r.column]; break;
       case Require::AtMostArg: hit = v->kind == json::Value::Number && v->num <= (double)nums[r.column]; break;
+      case Require::HashOfArg:
+        hit = hashed && !hashed[r.column].empty() && v->kind == json::Value::String && v->str.view() == hashed[r.column];
+        break;
+      case Require::IsString: hit = v->kind == json::Value::String; break;
     }
     if (hit) bits |= 1u << k;
   }
@@ -3025,16 +3164,17 @@ uint32_t requires_on(const json::Value& all_claims, const std::vector<Require>& 
 uint32_t MatchPlan::host_bits(const json::Value& claims, size_t i) const {
   std::string_view s[JG_MAX_ARGS * 4];               // a list over the caps may hold more columns than the scan takes
   int64_t v[JG_MAX_ARGS * 4];
+  const std::string* hx = hosted.empty() ? nullptr : &hosted[i * hashes->size()];
   if (strs->size() > JG_MAX_ARGS * 4 || nums->size() > JG_MAX_ARGS * 4) {
     std::vector<std::string_view> sv(strs->size());
     std::vector<int64_t> nv(nums->size());
     for (size_t c = 0; c < sv.size(); ++c) sv[c] = (*strs)[c][i];
     for (size_t c = 0; c < nv.size(); ++c) nv[c] = (*nums)[c][i];
-    return requires_on(claims, reqs, sv.data(), nv.data());
+    return requires_on(claims, reqs, sv.data(), nv.data(), hx);
   }
   for (size_t c = 0; c < strs->size(); ++c) s[c] = (*strs)[c][i];
   for (size_t c = 0; c < nums->size(); ++c) v[c] = (*nums)[c][i];
-  return requires_on(claims, reqs, s, v);
+  return requires_on(claims, reqs, s, v, hx);
 }
 }  // namespace
 
@@ -3045,7 +3185,7 @@ uint32_t match_requires(const json::Value& all_claims, const std::vector<Require
 
 uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs,
                         const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums) {
-  check_requires(reqs, true);
+  check_requires(reqs, Require::AtMostArg);
   for (const Require& r : reqs) {
     if (r.op == Require::EqualsArg && r.column >= strs.size())
       throw std::invalid_argument("capjwt: a requirement names a string column that was not given");
@@ -3053,6 +3193,23 @@ uint32_t match_requires(const json::Value& all_claims, const std::vector<Require
       throw std::invalid_argument("capjwt: a requirement names a number column that was not given");
   }
   return requires_on(all_claims, reqs, strs.data(), nums.data());
+}
+
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs,
+                        const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums,
+                        const std::vector<std::optional<std::string>>& hashed) {
+  check_requires(reqs, Require::IsString);
+  for (const Require& r : reqs) {
+    if (r.op == Require::EqualsArg && r.column >= strs.size())
+      throw std::invalid_argument("capjwt: a requirement names a string column that was not given");
+    if ((r.op == Require::AtLeastArg || r.op == Require::AtMostArg) && r.column >= nums.size())
+      throw std::invalid_argument("capjwt: a requirement names a number column that was not given");
+    if (r.op == Require::HashOfArg && r.column >= hashed.size())
+      throw std::invalid_argument("capjwt: a requirement names a hash column that was not given");
+  }
+  std::vector<std::string> hx(hashed.size());
+  for (size_t c = 0; c < hashed.size(); ++c) hx[c] = hashed[c] ? *hashed[c] : std::string();
+  return requires_on(all_claims, reqs, strs.data(), nums.data(), hx.data());
 }
 
 std::vector<MatchResult> Validator::MatchBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
@@ -3110,8 +3267,9 @@ void Validator::MatchVerdictsEach(const std::vector<std::string_view>& tokens, c
 std::vector<MatchResult> Validator::MatchBatchArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
                                                    const std::vector<Require>& requires_,
                                                    const std::vector<std::vector<std::string_view>>& strs,
-                                                   const std::vector<const int64_t*>& nums, CheckStats* stats) {
-  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+                                                   const std::vector<const int64_t*>& nums, CheckStats* stats,
+                                                   const std::vector<HashColumn>& hashes) {
+  const MatchPlan plan(requires_, tokens.size(), strs, nums, true, &hashes);
   std::vector<MatchResult> out(tokens.size());
   check_core<kMatchMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
                                 [&](size_t i, bool ok, std::string&& err, uint32_t bits) {
@@ -3126,8 +3284,8 @@ void Validator::MatchVerdictsArgs(const std::vector<std::string_view>& tokens, c
                                   const std::vector<Require>& requires_,
                                   const std::vector<std::vector<std::string_view>>& strs,
                                   const std::vector<const int64_t*>& nums, uint8_t* ok_out, uint32_t* bits_out,
-                                  CheckStats* stats) {
-  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+                                  CheckStats* stats, const std::vector<HashColumn>& hashes) {
+  const MatchPlan plan(requires_, tokens.size(), strs, nums, true, &hashes);
   check_core<kMatchMode, false>(ks_, tokens, &expected, 1, nullptr, stats,
                                 [&](size_t i, bool ok, std::string&&, uint32_t bits) {
                                   ok_out[i] = ok ? 1 : 0;
@@ -3140,9 +3298,10 @@ std::vector<MatchResult> Validator::MatchBatchArgsEach(const std::vector<std::st
                                                        const std::vector<uint32_t>& which,
                                                        const std::vector<Require>& requires_,
                                                        const std::vector<std::vector<std::string_view>>& strs,
-                                                       const std::vector<const int64_t*>& nums, CheckStats* stats) {
+                                                       const std::vector<const int64_t*>& nums, CheckStats* stats,
+                                                       const std::vector<HashColumn>& hashes) {
   each_args("MatchBatchArgsEach", tokens, expected, which);
-  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+  const MatchPlan plan(requires_, tokens.size(), strs, nums, true, &hashes);
   std::vector<MatchResult> out(tokens.size());
   check_core<kMatchMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
                                [&](size_t i, bool ok, std::string&& err, uint32_t bits) {
@@ -3157,9 +3316,9 @@ void Validator::MatchVerdictsArgsEach(const std::vector<std::string_view>& token
                                       const std::vector<uint32_t>& which, const std::vector<Require>& requires_,
                                       const std::vector<std::vector<std::string_view>>& strs,
                                       const std::vector<const int64_t*>& nums, uint8_t* ok_out, uint32_t* bits_out,
-                                      CheckStats* stats) {
+                                      CheckStats* stats, const std::vector<HashColumn>& hashes) {
   each_args("MatchVerdictsArgsEach", tokens, expected, which);
-  const MatchPlan plan(requires_, tokens.size(), strs, nums);
+  const MatchPlan plan(requires_, tokens.size(), strs, nums, true, &hashes);
   check_core<kMatchMode, true>(ks_, tokens, expected.data(), expected.size(), which.data(), stats,
                                [&](size_t i, bool ok, std::string&&, uint32_t bits) {
                                  ok_out[i] = ok ? 1 : 0;
@@ -3173,8 +3332,9 @@ void Validator::MatchVerdictsArgsEach(const std::vector<std::string_view>& token
 // any other device failure.  jg_claims_scan (CheckBatch), jg_claims_extract
 // (RegisteredBatch), jg_claims_select (SelectBatch), jg_claims_each (the *Each
 // entries: the three scans with a profile per job), jg_claims_paths (the
-// Select entries by path), jg_claims_match (the Match entries) and
-// jg_claims_match_args (the MatchArgs entries).
+// Select entries by path), jg_claims_match (the Match entries),
+// jg_claims_match_args (the MatchArgs entries) and jg_claims_match_hash (the
+// MatchArgs entries with a hash column, HashOfArg or IsString).
 extern "C" {
 __attribute__((weak)) int jg_claims_scan(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                          uint8_t*);
@@ -3191,6 +3351,9 @@ __attribute__((weak)) int jg_claims_match(jg_ctx*, const uint8_t*, size_t, const
 __attribute__((weak)) int jg_claims_match_args(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                                uint32_t, const jg_paths*, const jg_preds*, const jg_args*, uint8_t*,
                                                uint32_t*);
+__attribute__((weak)) int jg_claims_match_hash(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                               uint32_t, const jg_paths*, const jg_preds*, const jg_args*, const jg_hargs*,
+                                               uint8_t*, uint32_t*);
 }
 
 void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,
@@ -3249,6 +3412,17 @@ void Engine::claims_match_args(const uint8_t* arena, size_t arena_len, const voi
   abi_call("jg_claims_match_args", jg_claims_match_args != nullptr, inside_verify, [&] {
     return jg_claims_match_args(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
                                 (const jg_paths*)paths, (const jg_preds*)preds, (const jg_args*)args, codes, masks);
+  });
+}
+
+void Engine::claims_match_hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs,
+                               const void* expects, uint32_t nexpect, const void* paths, const void* preds,
+                               const void* args, const void* hargs, uint8_t* codes, uint32_t* masks,
+                               bool inside_verify) {
+  abi_call("jg_claims_match_hash", jg_claims_match_hash != nullptr, inside_verify, [&] {
+    return jg_claims_match_hash(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                                (const jg_paths*)paths, (const jg_preds*)preds, (const jg_args*)args,
+                                (const jg_hargs*)hargs, codes, masks);
   });
 }
 

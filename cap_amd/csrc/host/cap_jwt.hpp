@@ -223,6 +223,10 @@ class Engine {
   void claims_match_args(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                          uint32_t nexpect, const void* paths, const void* preds, const void* args, uint8_t* codes,
                          uint32_t* masks, bool inside_verify = false);
+  // ... and with hash columns (`hargs`, a jg_hargs) whose operands the device makes (jg_claims_match_hash)
+  void claims_match_hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                         uint32_t nexpect, const void* paths, const void* preds, const void* args, const void* hargs,
+                         uint8_t* codes, uint32_t* masks, bool inside_verify = false);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -521,11 +525,22 @@ struct ClaimPaths {
 //   AtLeast     v is a number f with f >= float64(bound); AtMost: f <= float64(bound)
 //   AtLeastArg  AtLeast with the token's entry in number column `column` as the
 //               bound; AtMostArg likewise
+// ... and, for the same entries, the two halves of an OIDC hash-claim check
+// (oidc/id_token.go verifyHashClaim; jg_claims_match_hash):
+//   HashOfArg   v is a string equal to base64.RawURLEncoding(SHA-2(x)[:size/2]) of
+//               the token's entry x in hash column `column`, with the SHA-2 of the
+//               token's own alg (RS/ES/PS256 -> SHA-256, 384 -> SHA-384, 512 ->
+//               SHA-512); never holds under EdDSA or for an absent entry
+//   IsString    v is a string ("" counts; null, numbers, arrays, objects do not)
+// Go's (verified, err) of IDToken.VerifyAccessToken is (IsString & HashOfArg,
+// err != nil exactly when IsString holds, HashOfArg does not and the alg is not
+// EdDSA).
 // The numbers are jg_pred_op's (include/jg.h).
 struct Require {
   enum Op : uint8_t {
     Equals = 1, HasWord = 2, HasElement = 3, Present = 4,
-    EqualsArg = 5, AtLeast = 6, AtMost = 7, AtLeastArg = 8, AtMostArg = 9
+    EqualsArg = 5, AtLeast = 6, AtMost = 7, AtLeastArg = 8, AtMostArg = 9,
+    HashOfArg = 10, IsString = 11
   };
   ClaimPath path;
   Op op = Present;
@@ -533,6 +548,9 @@ struct Require {
   int64_t bound = 0;
   uint32_t column = 0;
 };
+// One hash column of a MatchBatchArgs call: per token the value to hash (an
+// access token, an authorization code: any bytes), or nothing
+using HashColumn = std::vector<std::optional<std::string_view>>;
 // At most this many per call: the mask has one bit per requirement (JG_MAX_PRED)
 constexpr size_t kMaxRequires = 16;
 // CheckBatch's (ok, error string) and, for an accepted token, bit k set when
@@ -704,24 +722,37 @@ class Validator {
   // what MatchBatch throws for (an unknown op is one outside 1..9), a column whose
   // length is not the number of tokens, a column index without a column, and a
   // NUL byte in an operand.
+  // `hashes` holds the hash columns, each with one entry per token, for HashOfArg;
+  // IsString needs none.  A call with a hash column or one of these two ops goes
+  // through jg_claims_match_hash: the values are uploaded beside the tokens and
+  // hashed and encoded on the device, in front of the scan.  A token whose value is
+  // over JG_HASH_SRC_MAX bytes takes the host path, as do the tokens the scan
+  // leaves to it; there the digests come from one jg_hash_batch call over just
+  // those tokens' values.  More than JG_MAX_HASH_ARGS hash columns, or more than
+  // JG_MAX_ARGS string and hash columns together, send every token to the host
+  // path.  Throws also for a hash column whose length is not the number of tokens
+  // and a hash column index without a column; here an unknown op is one outside
+  // 1..11.
   std::vector<MatchResult> MatchBatchArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
                                           const std::vector<Require>& requires_,
                                           const std::vector<std::vector<std::string_view>>& strs,
-                                          const std::vector<const int64_t*>& nums, CheckStats* stats = nullptr);
+                                          const std::vector<const int64_t*>& nums, CheckStats* stats = nullptr,
+                                          const std::vector<HashColumn>& hashes = {});
   void MatchVerdictsArgs(const std::vector<std::string_view>& tokens, const Expected& expected,
                          const std::vector<Require>& requires_, const std::vector<std::vector<std::string_view>>& strs,
                          const std::vector<const int64_t*>& nums, uint8_t* ok, uint32_t* bits,
-                         CheckStats* stats = nullptr);
+                         CheckStats* stats = nullptr, const std::vector<HashColumn>& hashes = {});
   std::vector<MatchResult> MatchBatchArgsEach(const std::vector<std::string_view>& tokens,
                                               const std::vector<Expected>& expected, const std::vector<uint32_t>& which,
                                               const std::vector<Require>& requires_,
                                               const std::vector<std::vector<std::string_view>>& strs,
-                                              const std::vector<const int64_t*>& nums, CheckStats* stats = nullptr);
+                                              const std::vector<const int64_t*>& nums, CheckStats* stats = nullptr,
+                                          const std::vector<HashColumn>& hashes = {});
   void MatchVerdictsArgsEach(const std::vector<std::string_view>& tokens, const std::vector<Expected>& expected,
                              const std::vector<uint32_t>& which, const std::vector<Require>& requires_,
                              const std::vector<std::vector<std::string_view>>& strs,
                              const std::vector<const int64_t*>& nums, uint8_t* ok, uint32_t* bits,
-                             CheckStats* stats = nullptr);
+                             CheckStats* stats = nullptr, const std::vector<HashColumn>& hashes = {});
  private:
   KeySet* ks_;
 };
@@ -746,6 +777,15 @@ uint32_t match_requires(const json::Value& all_claims, const std::vector<Require
 // are its entries in column c.  What the host path of MatchBatchArgs runs.
 uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& requires_,
                         const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums);
+// ... and with one token's hash columns, already hashed: hashed[c] is
+// base64.RawURLEncoding(SHA-2(value)[:size/2]) of its entry in hash column c, or
+// nothing (an absent entry, EdDSA).  Takes HashOfArg and IsString too.
+uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& requires_,
+                        const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums,
+                        const std::vector<std::optional<std::string>>& hashed);
+// The value a hash claim must equal: base64.RawURLEncoding of the left half of a
+// digest (32, 48 or 64 bytes).  What the host path makes of jg_hash_batch's output.
+std::string hash_claim_value(const uint8_t* digest, int fam);
 // Expected's three leeways after Go's defaulting (jwt/jwt.go:128-170): the
 // clock skew in ns (negative -> 0, 0 -> one minute) and the leeways that
 // default a missing exp / nbf, as the whole seconds Go adds (negative -> 0,

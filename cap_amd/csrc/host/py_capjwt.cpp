@@ -435,6 +435,26 @@ PYBIND11_MODULE(_capjwt_host, m) {
       throw py::value_error(e.what());
     }
   });
+  m.def("match_requires_hash", [](py::bytes payload,
+                                  const std::vector<std::tuple<ClaimPath, int, std::string, int64_t, uint32_t>>& reqs,
+                                  const std::vector<std::string>& strs, const std::vector<int64_t>& nums,
+                                  const std::vector<std::optional<py::bytes>>& hashed) {
+    // the host path of MatchBatchArgs with one token's operands and its hash columns, already hashed
+    // and encoded (None: no value): the mask
+    json::Value v;
+    std::string err;
+    if (!json::parse(std::string(payload), &v, &err)) throw py::value_error(err);
+    std::vector<Require> rq;
+    for (const auto& [path, op, value, bound, column] : reqs)
+      rq.push_back(Require{path, (Require::Op)op, value, bound, column});
+    std::vector<std::optional<std::string>> hx;
+    for (const auto& h : hashed) hx.push_back(h ? std::optional<std::string>(std::string(*h)) : std::nullopt);
+    try {
+      return match_requires(v, rq, std::vector<std::string_view>(strs.begin(), strs.end()), nums, hx);
+    } catch (const std::invalid_argument& e) {
+      throw py::value_error(e.what());
+    }
+  });
   m.def("host_threads", &host_threads);
   m.def("set_host_memory_retention", &SetHostMemoryRetention);
   m.def("trim_host_memory", &TrimHostMemory);
@@ -777,21 +797,48 @@ PYBIND11_MODULE(_capjwt_host, m) {
       }
     }
   };
+  // The hash columns of a batch call: an entry is bytes or str (the value to hash) or None.  The texts are
+  // copied out while the GIL is held; the views point into the copies.
+  struct HashCols {
+    std::vector<std::vector<std::string>> store;
+    std::vector<HashColumn> cols;
+    explicit HashCols(const std::vector<py::sequence>& hashes) {
+      store.resize(hashes.size());
+      cols.resize(hashes.size());
+      for (size_t c = 0; c < hashes.size(); ++c) {
+        const size_t n = (size_t)py::len(hashes[c]);
+        store[c].resize(n);
+        cols[c].resize(n);
+        std::vector<uint8_t> has(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+          py::object o = hashes[c][i];
+          if (o.is_none()) continue;
+          if (!py::isinstance<py::bytes>(o) && !py::isinstance<py::str>(o))
+            throw py::type_error("a hash column holds bytes, str or None");
+          store[c][i] = o.cast<std::string>();
+          has[i] = 1;
+        }
+        for (size_t i = 0; i < n; ++i)
+          if (has[i]) cols[c][i] = std::string_view(store[c][i]);
+      }
+    }
+  };
   auto py_match_batch_args = [=](PyValidator& s, py::sequence toks, const ArgReqList& reqs,
                                  const std::vector<std::vector<std::string>>& strs, const std::vector<py::buffer>& nums,
-                                 const Who& who) {
+                                 const Who& who, const std::vector<py::sequence>& hashes) {
     // match_batch with the tokens' own operands: strs[c][i] and nums[c][i] are token i's in column c
     auto v = as_strings(toks);
     const std::vector<Require> rq = arg_requires_of(reqs);
     std::vector<std::vector<std::string_view>> sv;
     for (const auto& col : strs) sv.emplace_back(col.begin(), col.end());
     const NumCols nc(nums, v.size());
+    const HashCols hc(hashes);
     std::vector<MatchResult> rs;
     CheckStats st;
     {
       py::gil_scoped_release rel;
-      rs = who.es ? s.v->MatchBatchArgsEach(views(v), *who.es, *who.w, rq, sv, nc.cols, &st)
-                  : s.v->MatchBatchArgs(views(v), *who.e, rq, sv, nc.cols, &st);
+      rs = who.es ? s.v->MatchBatchArgsEach(views(v), *who.es, *who.w, rq, sv, nc.cols, &st, hc.cols)
+                  : s.v->MatchBatchArgs(views(v), *who.e, rq, sv, nc.cols, &st, hc.cols);
     }
     py::list out(rs.size());
     for (size_t i = 0; i < rs.size(); ++i) {
@@ -801,8 +848,10 @@ PYBIND11_MODULE(_capjwt_host, m) {
     return py::make_tuple(out, st.scanned, st.host);
   };
   auto py_match_blob_args = [=](PyValidator& s, py::bytes blob, const ArgReqList& reqs, const std::vector<py::bytes>& strs,
-                                const std::vector<py::buffer>& nums, const Who& who) {
-    // match_blob with the tokens' own operands: a string column is newline-separated bytes, as the tokens are
+                                const std::vector<py::buffer>& nums, const Who& who,
+                                const std::vector<py::bytes>& hashes) {
+    // match_blob with the tokens' own operands: a string column is newline-separated bytes, as the tokens are;
+    // so is a hash column, an empty line meaning "no value"
     char* bp = nullptr;
     Py_ssize_t bn = 0;
     if (PyBytes_AsStringAndSize(blob.ptr(), &bp, &bn) != 0) throw py::error_already_set();
@@ -816,14 +865,25 @@ PYBIND11_MODULE(_capjwt_host, m) {
       sv.push_back(split_operands(cp, (size_t)cn, toks.size()));
     }
     const NumCols nc(nums, toks.size());
+    std::vector<HashColumn> hv;
+    for (const py::bytes& col : hashes) {
+      char* cp = nullptr;
+      Py_ssize_t cn = 0;
+      if (PyBytes_AsStringAndSize(col.ptr(), &cp, &cn) != 0) throw py::error_already_set();
+      const std::vector<std::string_view> pieces = split_operands(cp, (size_t)cn, toks.size());
+      HashColumn hcol(pieces.size());
+      for (size_t i = 0; i < pieces.size(); ++i)
+        if (!pieces[i].empty()) hcol[i] = pieces[i];
+      hv.push_back(std::move(hcol));
+    }
     py::bytes ok = fresh_bytes(toks.size()), match = fresh_bytes(4 * toks.size());
     uint8_t* const okp = (uint8_t*)bytes_mem(ok);
     uint32_t* const mp = (uint32_t*)bytes_mem(match);
     CheckStats st;
     {
       py::gil_scoped_release rel;
-      if (who.es) s.v->MatchVerdictsArgsEach(toks, *who.es, *who.w, rq, sv, nc.cols, okp, mp, &st);
-      else s.v->MatchVerdictsArgs(toks, *who.e, rq, sv, nc.cols, okp, mp, &st);
+      if (who.es) s.v->MatchVerdictsArgsEach(toks, *who.es, *who.w, rq, sv, nc.cols, okp, mp, &st, hv);
+      else s.v->MatchVerdictsArgs(toks, *who.e, rq, sv, nc.cols, okp, mp, &st, hv);
     }
     py::dict d;
     d["ok"] = ok;
@@ -964,23 +1024,29 @@ PYBIND11_MODULE(_capjwt_host, m) {
       })
       .def("match_batch_args", [=](PyValidator& s, py::sequence toks, ArgReqList reqs,
                                    std::vector<std::vector<std::string>> strs, std::vector<py::buffer> nums,
-                                   const Expected& e) {
-        return py_match_batch_args(s, toks, reqs, strs, nums, Who{&e, nullptr, nullptr});
-      })
+                                   const Expected& e, std::vector<py::sequence> hashes) {
+        return py_match_batch_args(s, toks, reqs, strs, nums, Who{&e, nullptr, nullptr}, hashes);
+      }, py::arg("tokens"), py::arg("requires"), py::arg("strs"), py::arg("nums"), py::arg("expected"),
+         py::arg("hashes") = std::vector<py::sequence>())
       .def("match_batch_args_each", [=](PyValidator& s, py::sequence toks, ArgReqList reqs,
                                         std::vector<std::vector<std::string>> strs, std::vector<py::buffer> nums,
-                                        const std::vector<Expected>& es, const std::vector<uint32_t>& which) {
-        return py_match_batch_args(s, toks, reqs, strs, nums, Who{nullptr, &es, &which});
-      })
+                                        const std::vector<Expected>& es, const std::vector<uint32_t>& which,
+                                        std::vector<py::sequence> hashes) {
+        return py_match_batch_args(s, toks, reqs, strs, nums, Who{nullptr, &es, &which}, hashes);
+      }, py::arg("tokens"), py::arg("requires"), py::arg("strs"), py::arg("nums"), py::arg("expected"), py::arg("which"),
+         py::arg("hashes") = std::vector<py::sequence>())
       .def("match_blob_args", [=](PyValidator& s, py::bytes blob, ArgReqList reqs, std::vector<py::bytes> strs,
-                                  std::vector<py::buffer> nums, const Expected& e) {
-        return py_match_blob_args(s, blob, reqs, strs, nums, Who{&e, nullptr, nullptr});
-      })
+                                  std::vector<py::buffer> nums, const Expected& e, std::vector<py::bytes> hashes) {
+        return py_match_blob_args(s, blob, reqs, strs, nums, Who{&e, nullptr, nullptr}, hashes);
+      }, py::arg("blob"), py::arg("requires"), py::arg("strs"), py::arg("nums"), py::arg("expected"),
+         py::arg("hashes") = std::vector<py::bytes>())
       .def("match_blob_args_each", [=](PyValidator& s, py::bytes blob, ArgReqList reqs, std::vector<py::bytes> strs,
-                                       std::vector<py::buffer> nums, const std::vector<Expected>& es, py::buffer which) {
+                                       std::vector<py::buffer> nums, const std::vector<Expected>& es, py::buffer which,
+                                       std::vector<py::bytes> hashes) {
         const std::vector<uint32_t> w = which_of(which);
-        return py_match_blob_args(s, blob, reqs, strs, nums, Who{nullptr, &es, &w});
-      })
+        return py_match_blob_args(s, blob, reqs, strs, nums, Who{nullptr, &es, &w}, hashes);
+      }, py::arg("blob"), py::arg("requires"), py::arg("strs"), py::arg("nums"), py::arg("expected"), py::arg("which"),
+         py::arg("hashes") = std::vector<py::bytes>())
       .def("_concurrent_validate", [](PyValidator& s, py::bytes blob, const Expected& e, int callers,
                                       int64_t total, int pin_cpus) {
         // Measurement helper (bench.py `single`): `callers` host threads, each

@@ -51,6 +51,7 @@
 #include "kernels/ed25519.hpp"
 #include "kernels/claims.hpp"
 #include "kernels/hash.hpp"
+#include "kernels/hash_operand.hpp"
 #include "kernels/prep.hpp"
 #include "host_mont.hpp"
 #include "kernels/rsa.hpp"
@@ -721,6 +722,7 @@ struct Device {
   Grow cl_paths;                    // jg_claims_paths' resolved paths
   Grow cl_preds, cl_match;          // jg_claims_match's resolved predicates and its masks
   Grow cl_abytes, cl_astr, cl_anum; // jg_claims_match_args' operands: the bytes, the span table, the numbers
+  Grow cl_hbytes, cl_hsrc;          // jg_claims_match_hash's sources: the bytes to hash, the source table
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -3470,7 +3472,7 @@ int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
 
 namespace {
 
-// One scan of the claims: what the seven jg_claims_* entries hand to claims_run.
+// One scan of the claims: what the eight jg_claims_* entries hand to claims_run.
 // The resolved sides are host objects that `resolve` fills and points these at;
 // each is uploaded into the kept device buffer of its kind, and the kernel is
 // picked from which of them, and which outputs, are there (launch_claims).
@@ -3489,7 +3491,8 @@ struct ClaimsCall {
   const jgclaims::Preds* preds = nullptr;       // with paths and match_out: the masks in the place of the records
   uint32_t* match_out = nullptr;
   const jgclaims::ArgPreds* apreds = nullptr;   // in the place of preds, with args: the jobs' own operands
-  const jg_args* args = nullptr;
+  const jg_args* args = nullptr;                // NULL with apreds: no plain columns
+  const jg_hargs* hargs = nullptr;              // with apreds: the sources of the hashed string columns, behind args' own
 };
 
 const char kRefuseExpect[] = "more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9";
@@ -3514,6 +3517,13 @@ const char kRefuseArgPreds[] =
     "ASCII without quote and backslash, a space in a HAS_WORD value, more than 4 string or number "
     "columns, a column index that is not one byte below its count, a bound that is not 8 bytes, "
     "or two identical predicates";
+
+const char kRefuseHashPreds[] =
+    "more than 16 predicates, a path index past the paths, an op outside 1..11, a value that is "
+    "over 64 bytes, empty for HAS_WORD or HAS_ELEMENT, not empty for PRESENT or IS_STRING or not printable "
+    "ASCII without quote and backslash, a space in a HAS_WORD value, more than 4 string or number "
+    "columns, a column or hash column index that is not one byte below its count, a bound that is not "
+    "8 bytes, or two identical predicates";
 
 // The one path of a scan, after the entry's own NULL-argument test.  `resolve`
 // is the entry's resolve step: it fills the call's resolved sides and returns
@@ -3569,19 +3579,46 @@ int claims_run(jg_ctx* ctx, const std::string& entry, ClaimsCall& c, const std::
       else L.preds = (const jgclaims::Preds*)upload(d->cl_preds, c.preds, sizeof *c.preds);
       L.match_out = (uint32_t*)d->cl_match.get(sizeof(uint32_t) * njobs);
     }
+    std::vector<jg_sarg> rows;                         // the widened span table: alive until the stream is drained
     if (c.apreds) {
       // the operands: the bytes with the arena's slack behind them (the kernel reads them by aligned words)
-      const jg_args& A = *c.args;
-      uint8_t* ab = (uint8_t*)d->cl_abytes.get(A.bytes_len + ARENA_SLACK);
-      HIPCHK(hipMemsetAsync(ab + A.bytes_len, 0, ARENA_SLACK, s));
+      // The hashed columns (jg_claims_match_hash) are string columns nstr.. of the same two buffers: their
+      // operands lie behind the caller's bytes, 44 bytes per job and column from the next multiple of 4 on,
+      // and k_hash_operand writes them and their spans on this stream in front of the scan.
+      static const jg_args kNoArgs{};
+      const jg_args& A = c.args ? *c.args : kNoArgs;
+      const uint32_t nhash = c.hargs ? c.hargs->nhash : 0u, ncol = A.nstr + nhash;
+      const size_t hbase = nhash ? (A.bytes_len + 3) & ~(size_t)3 : A.bytes_len;
+      const size_t op_len = hbase + njobs * nhash * jghop::kSlot;
+      uint8_t* ab = (uint8_t*)d->cl_abytes.get(op_len + ARENA_SLACK);
+      if (hbase > A.bytes_len) HIPCHK(hipMemsetAsync(ab + A.bytes_len, 0, hbase - A.bytes_len, s));
+      HIPCHK(hipMemsetAsync(ab + op_len, 0, ARENA_SLACK, s));
       if (A.bytes_len) HIPCHK(hipMemcpyAsync(ab, A.bytes, A.bytes_len, hipMemcpyHostToDevice, s));
       L.arg_bytes = ab;
-      L.arg_str = (const jg_sarg*)d->cl_astr.get(sizeof(jg_sarg) * njobs * A.nstr);
-      if (A.nstr) HIPCHK(hipMemcpyAsync((void*)L.arg_str, A.str, sizeof(jg_sarg) * njobs * A.nstr, hipMemcpyHostToDevice, s));
+      jg_sarg* sp = (jg_sarg*)d->cl_astr.get(sizeof(jg_sarg) * njobs * ncol);
+      if (nhash && A.nstr) {                           // the caller's rows widened: the hashed columns' spans are the kernel's
+        rows.assign(njobs * ncol, jg_sarg{0u, 0u});
+        for (size_t i = 0; i < njobs; ++i)
+          for (uint32_t k = 0; k < A.nstr; ++k) rows[i * ncol + k] = A.str[i * A.nstr + k];
+        HIPCHK(hipMemcpyAsync(sp, rows.data(), sizeof(jg_sarg) * njobs * ncol, hipMemcpyHostToDevice, s));
+      } else if (A.nstr) {
+        HIPCHK(hipMemcpyAsync(sp, A.str, sizeof(jg_sarg) * njobs * A.nstr, hipMemcpyHostToDevice, s));
+      }
+      L.arg_str = sp;
       L.arg_num = (const int64_t*)d->cl_anum.get(sizeof(int64_t) * njobs * A.nnum);
       if (A.nnum) HIPCHK(hipMemcpyAsync((void*)L.arg_num, A.num, sizeof(int64_t) * njobs * A.nnum, hipMemcpyHostToDevice, s));
-      L.nstr = A.nstr;
+      L.nstr = ncol;
       L.nnum = A.nnum;
+      if (nhash) {
+        // the sources with the arena's slack behind them: the hash reads by aligned words
+        const jg_hargs& Hs = *c.hargs;
+        uint8_t* hb = (uint8_t*)d->cl_hbytes.get(Hs.bytes_len + ARENA_SLACK);
+        HIPCHK(hipMemsetAsync(hb + Hs.bytes_len, 0, ARENA_SLACK, s));
+        if (Hs.bytes_len) HIPCHK(hipMemcpyAsync(hb, Hs.bytes, Hs.bytes_len, hipMemcpyHostToDevice, s));
+        const jg_hsrc* hs = (const jg_hsrc*)upload(d->cl_hsrc, Hs.src, sizeof(jg_hsrc) * njobs * nhash);
+        launch_hash_operand(hb, hs, (int64_t)njobs, nhash, A.nstr, (uint32_t)hbase, ab, sp, s);
+        HIPCHK(hipGetLastError());
+      }
     }
     launch_claims(L, s);
     HIPCHK(hipGetLastError());
@@ -3739,6 +3776,58 @@ int jg_claims_match_args(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     c.paths = P.get();
     c.apreds = Q.get();
     c.args = args;
+    c.match_out = match_out;
+    return nullptr;
+  });
+}
+
+// jg_claims_match_args with string columns whose operands the device makes: the
+// resolved predicates name them as EQUALS_ARG on the columns behind the caller's
+// own, and two more uploads (the source bytes, the source table) feed the kernel
+// that writes them
+int jg_claims_match_hash(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                         const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
+                         const jg_paths* paths, const jg_preds* preds, const jg_args* args, const jg_hargs* hargs,
+                         uint8_t* code_out, uint32_t* match_out) {
+  if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out || !paths || !preds || !match_out)) ||
+      (arena_len > 0 && !arena))
+    return -1;
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, nullptr, nullptr};
+  auto T = std::make_unique<jgclaims::Profiles>();
+  auto P = std::make_unique<jgclaims::Paths>();
+  auto Q = std::make_unique<jgclaims::ArgPreds>();
+  std::string why;
+  return claims_run(ctx, "jg_claims_match_hash", c, [&]() -> const char* {
+    const uint32_t nstr = args ? args->nstr : 0u, nnum = args ? args->nnum : 0u, nhash = hargs ? hargs->nhash : 0u;
+    if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) return kRefuseProfiles;
+    if (!jgclaims::resolve_paths(*paths, P.get())) return kRefusePaths;
+    if (nhash > JG_MAX_HASH_ARGS || (nstr <= JG_MAX_ARGS && nstr + nhash > JG_MAX_ARGS))
+      return "more than 2 hash columns, or more than 4 string and hash columns together";
+    if (!jgclaims::resolve_arg_preds(*preds, *P, nstr, nnum, Q.get(), true, nhash)) return kRefuseHashPreds;
+    if (args && ((args->bytes_len && !args->bytes) || (nstr && !args->str) || (nnum && !args->num)))
+      return "the operands' bytes, spans or numbers are NULL";
+    if (hargs && ((hargs->bytes_len && !hargs->bytes) || (nhash && !hargs->src)))
+      return "the hash sources' bytes or table are NULL";
+    if (hargs && hargs->bytes_len >= (uint64_t(1) << 32) - ARENA_SLACK) return "the hash sources' bytes pass 4 GiB";
+    if ((args ? args->bytes_len : 0) + 4 + (uint64_t)njobs * nhash * jghop::kSlot >= (uint64_t(1) << 32) - ARENA_SLACK)
+      return "the operand bytes with the hashed columns pass 4 GiB";
+    for (size_t i = 0; i < njobs; ++i) {
+      if (args && !jgclaims::arg_operands_ok(*args, i)) {
+        why = "job " + std::to_string(i) + " has a string operand over 64 bytes, past the operand bytes or "
+              "with a byte that is not printable ASCII without quote and backslash";
+        return why.c_str();
+      }
+      if (nhash && !jgclaims::hash_sources_ok(*hargs, i)) {
+        why = "job " + std::to_string(i) + " has a hash source over 8192 bytes, past the source bytes or "
+              "with a family outside 0..3";
+        return why.c_str();
+      }
+    }
+    c.table = T.get();
+    c.paths = P.get();
+    c.apreds = Q.get();
+    c.args = args;
+    c.hargs = nhash ? hargs : nullptr;
     c.match_out = match_out;
     return nullptr;
   });

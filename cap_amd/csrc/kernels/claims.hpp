@@ -49,6 +49,10 @@
 // bytes per column, its length kept in a byte of one dword -- or a number with a
 // bound, the token's own or the list's: decided on integers of at most 15 digits
 // and left to the host (the one code a predicate changes) on any other number.
+// The same mode serves jg_claims_match_hash: IS_STRING is one more per-path mask
+// that the opening quote of the selected value sets, and EQUALS_HASH resolves to
+// EQUALS_ARG on a string column whose operand k_hash_operand wrote
+// (hash_operand.hpp), so the scan itself knows nothing about hashes.
 //
 // The expected side is a template parameter of the scan (EX: slen / sbyte / auds
 // and the window's edges).  Expect is one; ProfileRef, one profile of a
@@ -370,6 +374,7 @@ struct ArgPreds {
   uint32_t n;
   uint16_t all[JG_MAX_PATHS], present[JG_MAX_PATHS], str[JG_MAX_PATHS], word[JG_MAX_PATHS], elem[JG_MAX_PATHS];
   uint16_t num[JG_MAX_PATHS];                         // the numeric predicates on the path
+  uint16_t isstr[JG_MAX_PATHS];                       // IS_STRING (jg_claims_match_hash): set when the value begins with a quote
   uint16_t arg;                                       // the operand is the lane's: EQUALS_ARG, NUM_GE_ARG, NUM_LE_ARG
   uint16_t le;                                        // NUM_LE and NUM_LE_ARG; the other numeric ones are >=
   uint8_t op[JG_MAX_PRED];
@@ -378,9 +383,10 @@ struct ArgPreds {
   uint16_t off[JG_MAX_PRED];
   uint8_t pool[JG_MAX_PRED * JG_PRED_VALUE_MAX];
 };
-static_assert(sizeof(ArgPreds) == 128 + 4 + 6 * 16 + 4 + 3 * 16 + 32 + 1024 && sizeof(ArgPreds) % 8 == 0,
+static_assert(sizeof(ArgPreds) == 128 + 4 + 7 * 16 + 4 + 3 * 16 + 32 + 1024 && sizeof(ArgPreds) % 8 == 0,
               "no padding in the predicates with operands");
 static_assert(JG_MAX_ARGS == 4 && JG_PRED_VALUE_MAX <= 255, "four operand lengths in one dword");
+static_assert(JG_MAX_HASH_ARGS <= JG_MAX_ARGS, "a hashed column is a string column of the kernel");
 
 // Fills *Q from the ABI's jg_preds as jg_claims_match_args reads it, for the
 // resolved paths P and the column counts of the same call.  Ops 1..4 are held to
@@ -388,19 +394,29 @@ static_assert(JG_MAX_ARGS == 4 && JG_PRED_VALUE_MAX <= 255, "four operand length
 // EQUALS_ARG or NUM_*_ARG whose value is not one byte below its column count, a
 // NUM_GE / NUM_LE whose value is not eight bytes (B, little-endian), two identical
 // predicates (for an ARG one: the same path, op and column).
-inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, uint32_t nnum, ArgPreds* Q) {
+// With hash_ops (jg_claims_match_hash) the list may also hold JG_PRED_EQUALS_HASH
+// -- one value byte, the hash column h < nhash; resolved to EQUALS_ARG on string
+// column nstr + h, where the device writes that job's operand -- and
+// JG_PRED_IS_STRING (no value).  False also for: nhash over JG_MAX_HASH_ARGS,
+// nstr + nhash over JG_MAX_ARGS, two EQUALS_HASH of one path and column, two
+// IS_STRING of one path.
+inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, uint32_t nnum, ArgPreds* Q,
+                              bool hash_ops = false, uint32_t nhash = 0) {
   if (x.n > JG_MAX_PRED || nstr > JG_MAX_ARGS || nnum > JG_MAX_ARGS) return false;
+  if (nhash > JG_MAX_HASH_ARGS || nstr + nhash > JG_MAX_ARGS || (nhash && !hash_ops)) return false;
   *Q = ArgPreds{};
-  uint8_t path[JG_MAX_PRED] = {};
+  uint8_t path[JG_MAX_PRED] = {}, rawop[JG_MAX_PRED] = {};
   uint32_t vlen[JG_MAX_PRED] = {}, voff[JG_MAX_PRED] = {};        // within x.values
   uint32_t o = 0, po = 0;                                         // within x.values, within the pool
   for (uint32_t k = 0; k < x.n; ++k) {
     const uint32_t p = x.path[k], op = x.op[k], l = x.value_len[k];
-    if (p >= P.n || op < JG_PRED_EQUALS || op > JG_PRED_NUM_LE_ARG) return false;
+    if (p >= P.n || op < JG_PRED_EQUALS || op > (hash_ops ? (uint32_t)JG_PRED_IS_STRING : (uint32_t)JG_PRED_NUM_LE_ARG))
+      return false;
     const bool konst = op <= JG_PRED_PRESENT;
-    const bool arg = op == JG_PRED_EQUALS_ARG || op == JG_PRED_NUM_GE_ARG || op == JG_PRED_NUM_LE_ARG;
-    const bool num = op >= JG_PRED_NUM_GE;
-    const uint32_t lo = konst ? (op == JG_PRED_EQUALS || op == JG_PRED_PRESENT ? 0u : 1u) : arg ? 1u : 8u;
+    const bool hash = op == JG_PRED_EQUALS_HASH, isstr = op == JG_PRED_IS_STRING;
+    const bool arg = op == JG_PRED_EQUALS_ARG || op == JG_PRED_NUM_GE_ARG || op == JG_PRED_NUM_LE_ARG || hash;
+    const bool num = op >= JG_PRED_NUM_GE && op <= JG_PRED_NUM_LE_ARG;
+    const uint32_t lo = konst ? (op == JG_PRED_EQUALS || op == JG_PRED_PRESENT ? 0u : 1u) : arg ? 1u : isstr ? 0u : 8u;
     const uint32_t hi = konst ? (op == JG_PRED_PRESENT ? 0u : (uint32_t)JG_PRED_VALUE_MAX) : lo;
     if (l < lo || l > hi || (l && !x.values)) return false;
     if (konst) {
@@ -413,19 +429,20 @@ inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, 
       Q->off[k] = (uint16_t)po;
       po += l;
     } else if (arg) {
-      if (x.values[o] >= (op == JG_PRED_EQUALS_ARG ? nstr : nnum)) return false;
-      Q->col[k] = x.values[o];
-    } else {
+      if (x.values[o] >= (hash ? nhash : op == JG_PRED_EQUALS_ARG ? nstr : nnum)) return false;
+      Q->col[k] = (uint8_t)(x.values[o] + (hash ? nstr : 0u));
+    } else if (!isstr) {
       uint64_t b8 = 0;
       for (uint32_t b = 0; b < 8u; ++b) b8 |= (uint64_t)x.values[o + b] << (8u * b);
       Q->bound[k] = (int64_t)b8;
     }
     path[k] = (uint8_t)p;
-    Q->op[k] = (uint8_t)op;
+    rawop[k] = (uint8_t)op;
+    Q->op[k] = (uint8_t)(hash ? (uint32_t)JG_PRED_EQUALS_ARG : op);   // the scan's form
     vlen[k] = l;
     voff[k] = o;
     for (uint32_t j = 0; j < k; ++j) {
-      if (path[j] != p || Q->op[j] != op || vlen[j] != l) continue;
+      if (path[j] != p || rawop[j] != op || vlen[j] != l) continue;
       uint32_t b = 0;
       while (b < l && x.values[voff[j] + b] == x.values[o + b]) ++b;
       if (b == l) return false;
@@ -433,10 +450,11 @@ inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, 
     const uint16_t bit = (uint16_t)(1u << k);
     Q->all[p] |= bit;
     if (op == JG_PRED_PRESENT) Q->present[p] |= bit;
-    if (op == JG_PRED_EQUALS || op == JG_PRED_HAS_WORD || op == JG_PRED_EQUALS_ARG) Q->str[p] |= bit;
+    if (op == JG_PRED_EQUALS || op == JG_PRED_HAS_WORD || op == JG_PRED_EQUALS_ARG || hash) Q->str[p] |= bit;
     if (op == JG_PRED_HAS_WORD) Q->word[p] |= bit;
     if (op == JG_PRED_HAS_ELEMENT) Q->elem[p] |= bit;
     if (num) Q->num[p] |= bit;
+    if (isstr) Q->isstr[p] |= bit;
     if (arg) Q->arg |= bit;
     if (op == JG_PRED_NUM_LE || op == JG_PRED_NUM_LE_ARG) Q->le |= bit;
     o += l;
@@ -454,6 +472,17 @@ inline bool arg_operands_ok(const jg_args& a, size_t i) {
     if (s.len > JG_PRED_VALUE_MAX || s.off > a.bytes_len || s.len > a.bytes_len - s.off) return false;
     for (uint32_t b = 0; b < s.len; ++b)
       if (!name_byte_ok(a.bytes[s.off + b])) return false;
+  }
+  return true;
+}
+
+// One job's sources as jg_claims_match_hash checks them before the launch: every
+// span within `bytes`, at most JG_HASH_SRC_MAX bytes, a family in 0..3.  False:
+// job i's sources are refused.
+inline bool hash_sources_ok(const jg_hargs& h, size_t i) {
+  for (uint32_t c = 0; c < h.nhash; ++c) {
+    const jg_hsrc& s = h.src[i * h.nhash + c];
+    if (s.fam > JG_SHA512 || s.len > JG_HASH_SRC_MAX || s.off > h.bytes_len || s.len > h.bytes_len - s.off) return false;
   }
   return true;
 }
@@ -710,7 +739,10 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const PQ* Q = nu
     s.mcand = !str ? 0u : slot ? Q->str[slot - 1u] : el ? Q->elem[el - 1u] : 0u;
     s.mword = str && slot ? Q->word[slot - 1u] : 0u;
     s.wpos = 0;
-    if constexpr (M == kMatchArgs) s.nump = slot ? Q->num[slot - 1u] : 0u;   // read by end_number, if this is one
+    if constexpr (M == kMatchArgs) {
+      s.nump = slot ? Q->num[slot - 1u] : 0u;          // read by end_number, if this is one
+      s.res |= str && slot ? Q->isstr[slot - 1u] : 0u; // IS_STRING holds from the opening quote; "" counts
+    }
     if (c == '[' && slot) {
       s.marr = slot;
       s.medepth = s.depth + 1u;

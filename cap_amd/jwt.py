@@ -239,7 +239,9 @@ class ArgRequire(tuple):
     forms, beside Require's: (path, op, "", bound, column).  Built by EqualsEach,
     AtLeast, AtMost, AtLeastEach and AtMostEach."""
     EQUALS_ARG, NUM_GE, NUM_LE, NUM_GE_ARG, NUM_LE_ARG = 5, 6, 7, 8, 9     # jg_pred_op (include/jg.h)
-    _NAMES = {5: "EqualsEach", 6: "AtLeast", 7: "AtMost", 8: "AtLeastEach", 9: "AtMostEach"}
+    EQUALS_HASH, IS_STRING = 10, 11
+    _NAMES = {5: "EqualsEach", 6: "AtLeast", 7: "AtMost", 8: "AtLeastEach", 9: "AtMostEach", 10: "HashOfEach",
+              11: "IsString"}
 
     def __new__(cls, path_or_name, op, bound=0, column=0):
         path = path_or_name if isinstance(path_or_name, Path) else Path(path_or_name)
@@ -251,6 +253,8 @@ class ArgRequire(tuple):
         return super().__new__(cls, (path, int(op), "", bound, column))
 
     def __repr__(self):
+        if self[1] == self.IS_STRING:
+            return "IsString(%r)" % (self[0],)
         return "%s(%r, %r)" % (self._NAMES.get(self[1], "ArgRequire"), self[0],
                                self[3] if self[1] in (self.NUM_GE, self.NUM_LE) else self[4])
 
@@ -280,6 +284,18 @@ def AtMostEach(path_or_name, column: int) -> ArgRequire:
     return ArgRequire(path_or_name, ArgRequire.NUM_LE_ARG, column=column)
 
 
+def HashOfEach(path_or_name, column: int) -> ArgRequire:
+    """The claim is a string equal to base64url(SHA-2(x)[:half]) of the token's own entry x in hash column
+    `column`, with the SHA-2 of the token's alg: what at_hash is to the access token and c_hash to the
+    authorization code (oidc/id_token.go verifyHashClaim).  Never holds under EdDSA or for a None entry."""
+    return ArgRequire(path_or_name, ArgRequire.EQUALS_HASH, column=column)
+
+
+def IsString(path_or_name) -> ArgRequire:
+    """The claim is a string ("" counts; null, numbers, arrays and objects do not)."""
+    return ArgRequire(path_or_name, ArgRequire.IS_STRING)
+
+
 def _arg_requires_of(requires):
     out = []
     for r in requires:
@@ -289,7 +305,7 @@ def _arg_requires_of(requires):
             out.append((list(r[0]), r[1], r[2], r[3], r[4]))
         else:
             raise TypeError("requires: elements are built by Equals, HasWord, HasElement, Present, EqualsEach, "
-                            "AtLeast, AtMost, AtLeastEach or AtMostEach")
+                            "AtLeast, AtMost, AtLeastEach, AtMostEach, HashOfEach or IsString")
     return out
 
 
@@ -542,7 +558,7 @@ class Validator:
 
     # ---- ... with an operand per token, and numeric tests
     def MatchBatchArgs(self, tokens: Sequence, requires: Sequence, strs: Sequence = (), nums: Sequence = (),
-                       expected: Expected = None, stats: dict = None):
+                       expected: Expected = None, stats: dict = None, hashes: Sequence = ()):
         """MatchBatch for the checks whose other side differs from token to token: the
         nonce of that request, auth_time under its max_age, sub against the session's
         subject.  `requires` may also hold EqualsEach(path, c) -- the claim equals
@@ -557,41 +573,57 @@ class Validator:
         answered from the host path, as is every token of a list over the scan's caps
         (MatchBatch's, or more than 4 columns of a kind).  A column whose length is
         not len(tokens), a column index without a column, more than 16 requirements,
-        a NUL in an operand: ValueError."""
+        a NUL in an operand: ValueError.
+
+        `hashes`: hash columns, one entry of bytes / str / None per token, for
+        HashOfEach(path, c): the claim equals base64url(SHA-2(hashes[c][i])[:half])
+        with the SHA-2 of tokens[i]'s alg -- at_hash against the access token, c_hash
+        against the authorization code -- hashed and encoded on the device in front of
+        the scan.  With IsString(path) the pair maps to Go's (verified, err) of
+        IDToken.VerifyAccessToken / VerifyAuthorizationCode: verified = IsString &
+        HashOfEach; err != nil exactly when IsString holds, HashOfEach does not and
+        the alg is not EdDSA.  A value over 8192 bytes is hashed on the host path.
+        At most 2 hash columns, and 4 string and hash columns together, are scanned.
+        A hash column whose length is not len(tokens), or a hash column index without
+        a column: ValueError."""
         rows, scanned, host = self._impl.match_batch_args(list(tokens), _arg_requires_of(requires),
                                                           [list(c) for c in strs], _num_columns(nums),
-                                                          (expected or Expected())._native())
+                                                          (expected or Expected())._native(), [list(c) for c in hashes])
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return [tuple(r) for r in rows]
 
     def MatchBlobArgs(self, blob: bytes, requires: Sequence, strs: Sequence = (), nums: Sequence = (),
-                      expected: Expected = None, stats: dict = None) -> dict:
+                      expected: Expected = None, stats: dict = None, hashes: Sequence = ()) -> dict:
         """MatchBatchArgs' throughput form: newline-separated tokens and, per string
         column, newline-separated operands (bytes; an empty line is the operand "")
-        -> MatchBlob's columns."""
+        -> MatchBlob's columns.  A hash column is newline-separated values too; an
+        empty line means "no value"."""
         cols, scanned, host = self._impl.match_blob_args(blob, _arg_requires_of(requires), [bytes(c) for c in strs],
-                                                         _num_columns(nums), (expected or Expected())._native())
+                                                         _num_columns(nums), (expected or Expected())._native(),
+                                                         [bytes(c) for c in hashes])
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return cols
 
     def MatchBatchArgsEach(self, tokens: Sequence, requires: Sequence, expected: Sequence[Expected],
-                           which: Sequence[int], strs: Sequence = (), nums: Sequence = (), stats: dict = None):
+                           which: Sequence[int], strs: Sequence = (), nums: Sequence = (), stats: dict = None,
+                           hashes: Sequence = ()):
         """MatchBatchArgs with expected[which[i]] for tokens[i]."""
         rows, scanned, host = self._impl.match_batch_args_each(list(tokens), _arg_requires_of(requires),
                                                                [list(c) for c in strs], _num_columns(nums),
-                                                               self._natives(expected), list(which))
+                                                               self._natives(expected), list(which),
+                                                               [list(c) for c in hashes])
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return [tuple(r) for r in rows]
 
     def MatchBlobArgsEach(self, blob: bytes, requires: Sequence, expected: Sequence[Expected], which,
-                          strs: Sequence = (), nums: Sequence = (), stats: dict = None) -> dict:
+                          strs: Sequence = (), nums: Sequence = (), stats: dict = None, hashes: Sequence = ()) -> dict:
         """MatchBlobArgs with expected[which[i]] for token i; `which` as in CheckBlobEach."""
         cols, scanned, host = self._impl.match_blob_args_each(blob, _arg_requires_of(requires),
                                                               [bytes(c) for c in strs], _num_columns(nums),
-                                                              self._natives(expected), which)
+                                                              self._natives(expected), which, [bytes(c) for c in hashes])
         if stats is not None:
             stats.update(scanned=scanned, host=host)
         return cols
@@ -607,4 +639,4 @@ __all__ = ["RS256", "RS384", "RS512", "ES256", "ES384", "ES512", "PS256", "PS384
            "DefaultLeewaySeconds", "PublicKey", "SupportedSigningAlgorithm", "ParsePublicKeyPEM", "KeySet",
            "NewStaticKeySet", "NewJSONWebKeySet", "NewOIDCDiscoveryKeySet", "Expected", "Path", "Validator",
            "NewValidator", "Require", "Equals", "HasWord", "HasElement", "Present", "ArgRequire", "EqualsEach",
-           "AtLeast", "AtMost", "AtLeastEach", "AtMostEach"]
+           "AtLeast", "AtMost", "AtLeastEach", "AtMostEach", "HashOfEach", "IsString"]

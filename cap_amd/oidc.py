@@ -8,6 +8,14 @@ Host work (UnmarshalClaims, go-jose ParseSigned, the alg checks, base64url)
 runs in the C++ host mirror (cap_amd/csrc/host/cap_jwt.hpp); the hashes of a
 batch run in one jg_hash_batch on the GPU.  Go's `(bool, error)` becomes
 `(verified, err)` with err a str or None; the strings are the reference's.
+
+A caller that already runs the tokens through jwt.Validator.MatchBatchArgs /
+MatchBlobArgs (the nonce, auth_time) gets the same answer in that one call,
+without this second pass: jwt.HashOfEach("at_hash", c) and jwt.IsString("at_hash")
+with the access tokens as hash column c (`hashes=`), hashed and compared on the
+device -- verified = IsString & HashOfEach, err != nil exactly when IsString
+holds, HashOfEach does not and the alg is not EdDSA.  The entries here stay for
+unverified tokens and for Go's error strings.
 """
 import threading
 from typing import List, Optional, Sequence, Tuple

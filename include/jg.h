@@ -680,6 +680,61 @@ int jg_claims_match_args(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                          const jg_expect* expects, uint32_t nexpect, const jg_paths* paths, const jg_preds* preds,
                          const jg_args* args, uint8_t* code_out, uint32_t* match_out);
 
+/* ---- predicates on a hash claim: at_hash, c_hash ----
+ * jg_claims_match_args for the one per-request check of an OIDC callback whose
+ * other side is not a value the caller holds but the hash of one
+ * (oidc/id_token.go:59-145, IDToken.VerifyAccessToken / VerifyAuthorizationCode
+ * -> verifyHashClaim): the claim must be a string equal to
+ * base64.RawURLEncoding(SHA-2(access token)[:size/2]).  The same jobs,
+ * profiles, paths, preds, args, code_out and match_out, and `hargs`: nhash hash
+ * columns, job i's source in column h being bytes[off, off + len) of
+ * src[i * nhash + h], hashed with `fam` (SHA-256 / 384 / 512, the family of the
+ * id_token's alg; 0 = this job has no value, as under EdDSA).  A kernel of its
+ * own (kernels/hash_operand.hip) hashes every source, encodes the left half of
+ * the digest -- 22, 32 or 43 characters -- and writes it as that job's operand in
+ * string column nstr + h of the operands jg_claims_match_args' kernel reads, on
+ * the scan's stream in front of the scan: no digest comes back to the host.  Two
+ * more ops, with v the value the walk reaches as for the other nine:
+ *  - JG_PRED_EQUALS_HASH: v is a string whose bytes equal that encoding for job
+ *    i's source in hash column h.  value_len is 1 and the value byte is h
+ *    (< nhash).  Never set for a job whose fam is 0.  What JG_PRED_EQUALS_ARG
+ *    says about bytes >= 0x80 and about a key named twice holds here too;
+ *  - JG_PRED_IS_STRING: the walk reaches a string; "" counts, null, numbers,
+ *    literals, arrays and objects do not.  value_len is 0.
+ * In Go's terms (verified, err) of VerifyAccessToken is (IS_STRING &
+ * EQUALS_HASH, err != nil exactly when IS_STRING holds, EQUALS_HASH does not and
+ * the alg is not EdDSA).
+ * Neither op changes a code and no payload is JG_CL_HOST because of them.  With
+ * no op >= 10 and nhash == 0 the outputs are jg_claims_match_args', byte for
+ * byte.  Source bytes are any bytes, at most JG_HASH_SRC_MAX per source; a
+ * longer value is the host's to hash.
+ * Everything else is jg_claims_match_args' (two more kept buffers: the source
+ * bytes and the source table; the operand bytes and the span table are sized
+ * for nstr + nhash columns, 44 bytes and a span per job and hash column).
+ * -1: everything jg_claims_match_args refuses (its unknown ops are here those
+ * outside 1..11; args may be NULL: no plain columns); nhash over
+ * JG_MAX_HASH_ARGS; args->nstr + nhash over JG_MAX_ARGS; a hash column index
+ * that is not below nhash; two EQUALS_HASH of one path and column; two
+ * IS_STRING of one path; bytes NULL with bytes_len > 0 or src NULL with nhash >
+ * 0; bytes_len of 2^32 or more; and, naming the job: a len over
+ * JG_HASH_SRC_MAX, a span past bytes_len, a fam outside 0..3.  hargs may be
+ * NULL: nhash 0. */
+#define JG_MAX_HASH_ARGS 2
+#define JG_HASH_SRC_MAX 8192
+enum { JG_PRED_EQUALS_HASH = 10, JG_PRED_IS_STRING = 11 };   /* jg_claims_match_hash only */
+typedef struct jg_hsrc { uint32_t off, len; uint8_t fam; uint8_t pad_[3]; } jg_hsrc;  /* fam: jg_hash_fam, or 0 = no value */
+typedef struct jg_hargs {
+  const uint8_t* bytes; size_t bytes_len;    /* the values to hash: any bytes */
+  const jg_hsrc* src;                        /* njobs x nhash, job-major */
+  uint32_t nhash, pad_;                      /* 0..JG_MAX_HASH_ARGS */
+} jg_hargs;
+int jg_claims_match_hash(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                         const jg_cjob* jobs, size_t njobs,
+                         const jg_expect* expects, uint32_t nexpect, const jg_paths* paths, const jg_preds* preds,
+                         const jg_args* args /* may be NULL: no plain columns */,
+                         const jg_hargs* hargs /* may be NULL: nhash 0 */,
+                         uint8_t* code_out, uint32_t* match_out);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 

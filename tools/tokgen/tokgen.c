@@ -114,10 +114,12 @@ static void* worker(void* arg) {
   const char* extra = getenv("TOKGEN_EXTRA");
   if (!extra) extra = "";
   /* TOKGEN_OIDC=1: token i also carries "nonce":"n-<i as 20 hex digits>" (22 bytes, its own) and
-   * "auth_time":1611699344 - i % 3600, in front of TOKGEN_EXTRA's members */
+   * "auth_time":1611699344 - i % 3600, in front of TOKGEN_EXTRA's members.
+   * TOKGEN_OIDC=2: and "at_hash", the left half of the alg's SHA-2 of the access token "ya29.<i as 35 hex
+   * digits>" (40 bytes, its own) as unpadded base64url (oidc/id_token.go verifyHashClaim); EdDSA: SHA-512 */
   const char* oe = getenv("TOKGEN_OIDC");
-  const int oidc = oe && atol(oe) != 0;
-  char oidcv[96] = "";
+  const int oidc = oe ? (int)atol(oe) : 0;
+  char oidcv[192] = "";
   /* TOKGEN_TENANTS=P: token i belongs to tenant i % P, with an issuer and an
    * audience of its own of the default ones' lengths ("https://t07.example/",
    * "c07.example.com"); unset or 0: the default issuer and audience */
@@ -141,6 +143,17 @@ static void* worker(void* arg) {
     }
     snprintf(hdr, sizeof hdr, "{\"alg\":\"%s\",\"kid\":\"kid-%02d\",\"typ\":\"JWT\"}", j->alg, j->kid_base + k);
     if (oidc) snprintf(oidcv, sizeof oidcv, "\"nonce\":\"n-%020lx\",\"auth_time\":%ld,", i, 1611699344L - i % 3600);
+    if (oidc == 2) {
+      char at[48], ah[96];
+      unsigned char dg[EVP_MAX_MD_SIZE];
+      unsigned dl = 0;
+      snprintf(at, sizeof at, "ya29.%035lx", i);
+      const EVP_MD* hm = alg_md(j->alg);
+      if (EVP_Digest(at, strlen(at), dg, &dl, hm ? hm : EVP_sha512(), NULL) != 1) { fprintf(stderr, "at_hash digest\n"); exit(2); }
+      ah[b64url(dg, dl / 2, ah)] = 0;
+      const size_t ol = strlen(oidcv);
+      snprintf(oidcv + ol, sizeof oidcv - ol, "\"at_hash\":\"%s\",", ah);
+    }
     if (padn)
       snprintf(pay, cap,
                "{\"aud\":[\"%s\"],\"exp\":1611699944,\"iat\":1611699344,"
