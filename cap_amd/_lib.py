@@ -28,7 +28,8 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_keys_table_widths", "jg_debug_fail_alloc", "jg_debug_table_digest", "jg_debug_table_read",
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
            "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
-           "jg_claims_paths", "jg_claims_match", "jg_claims_match_args", "jg_claims_match_hash"]
+           "jg_claims_paths", "jg_claims_match", "jg_claims_match_args", "jg_claims_match_hash",
+           "jg_set_load", "jg_set_free", "jg_set_info", "jg_debug_set_read", "jg_claims_match_set"]
 
 
 class JgKey(ctypes.Structure):
@@ -163,6 +164,34 @@ class JgHArgs(ctypes.Structure):
 
 
 assert ctypes.sizeof(JgHSrc) == 12 and ctypes.sizeof(JgHArgs) == 32
+
+
+# ... and those only jg_claims_match_set takes: the value is a set index of the call (one byte)
+PRED_IN_SET, PRED_ELEMENT_IN_SET = 12, 13
+MAX_SETS, MAX_LOADED_SETS, SET_MEMBER_MAX = 4, 16, 255   # JG_MAX_SETS, JG_MAX_LOADED_SETS, JG_SET_MEMBER_MAX
+
+
+class JgSetInfo(ctypes.Structure):
+    """jg_setinfo: what jg_set_info reports of a loaded set"""
+    _fields_ = [("n", ctypes.c_uint32), ("nslots", ctypes.c_uint32), ("maxprobe", ctypes.c_uint32),
+                ("seed", ctypes.c_uint32), ("pool_bytes", ctypes.c_uint64), ("generation", ctypes.c_uint64)]
+
+
+class JgSetArgs(ctypes.Structure):
+    """jg_setargs: the loaded sets a jg_claims_match_set call names"""
+    _fields_ = [("nsets", ctypes.c_uint32), ("id", ctypes.c_uint32 * MAX_SETS)]
+
+
+assert ctypes.sizeof(JgSetInfo) == 32 and ctypes.sizeof(JgSetArgs) == 20
+
+
+def _jg_setargs(ids, nsets=None):
+    """Set ids -> JgSetArgs (ids past what the struct holds are dropped: the call is refused on its count)"""
+    g = JgSetArgs()
+    g.nsets = len(ids) if nsets is None else nsets
+    for k, x in enumerate(list(ids)[:MAX_SETS]):
+        g.id[k] = x
+    return g
 
 
 def pack_hargs(cols=(), lead=0):
@@ -382,6 +411,14 @@ def lib():
         L.jg_claims_match_hash.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
                                            ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds),
                                            ctypes.POINTER(JgArgs), ctypes.POINTER(JgHArgs), vp, vp]
+        L.jg_claims_match_set.argtypes = [vp, vp, sz, ctypes.POINTER(JgCJob), sz, ctypes.POINTER(JgExpect),
+                                          ctypes.c_uint32, ctypes.POINTER(JgPaths), ctypes.POINTER(JgPreds),
+                                          ctypes.POINTER(JgArgs), ctypes.POINTER(JgHArgs), ctypes.POINTER(JgSetArgs),
+                                          vp, vp]
+        L.jg_set_load.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz, ctypes.c_uint32]
+        L.jg_set_free.argtypes = [vp, ctypes.c_uint32]
+        L.jg_set_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(JgSetInfo)]
+        L.jg_debug_set_read.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz]
         L.jg_keys_wait_tables.argtypes = [vp]
         L.jg_keys_table_widths.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         L.jg_debug_fail_alloc.argtypes = [vp, ctypes.c_int]
@@ -740,6 +777,77 @@ class Context:
                           None if "preds" in null else ctypes.byref(qs),
                           None if ga is None else ctypes.byref(ga),
                           None if gh is None else ctypes.byref(gh),
+                          None if "codes" in null else out,
+                          None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
+        return out.raw[:n], list(masks[:n])
+
+    def set_load(self, set_id, members, seed=0, spans=None):
+        """jg_set_load: set `set_id` of the context = `members` (a list of bytes),
+        built under `seed`.  `spans` overrides the (off, len) rows handed to the ABI
+        over the members' bytes back to back (for its argument checks)."""
+        members = [bytes(m) for m in members]
+        blob = b"".join(members)
+        if spans is None:
+            spans, o = [], 0
+            for m in members:
+                spans.append((o, len(m)))
+                o += len(m)
+        sp = (JgSArg * max(1, len(spans)))()
+        for t, (off, ln) in zip(sp, spans):
+            t.off, t.len = off, ln
+        rc = lib().jg_set_load(self.h, int(set_id), blob or b"\0", len(blob), ctypes.cast(sp, ctypes.c_void_p),
+                               len(spans), int(seed) & 0xffffffff)
+        if rc != 0:
+            raise JgError(f"jg_set_load rc={rc}: {self.error()}")
+
+    def set_free(self, set_id):
+        """jg_set_free"""
+        rc = lib().jg_set_free(self.h, int(set_id))
+        if rc != 0:
+            raise JgError(f"jg_set_free rc={rc}: {self.error()}")
+
+    def set_info(self, set_id):
+        """jg_set_info -> {"n", "nslots", "maxprobe", "seed", "pool_bytes", "generation"}"""
+        out = JgSetInfo()
+        rc = lib().jg_set_info(self.h, int(set_id), ctypes.byref(out))
+        if rc != 0:
+            raise JgError(f"jg_set_info rc={rc}: {self.error()}")
+        return {k: int(getattr(out, k)) for k, _ in JgSetInfo._fields_}
+
+    def set_read(self, set_id):
+        """jg_debug_set_read -> (slots: list of (hash, ref), pool: list of dwords) as they lie on the device"""
+        info = self.set_info(set_id)
+        ns, nd = info["nslots"], info["pool_bytes"] // 4
+        slots, pool = (ctypes.c_uint32 * (2 * ns))(), (ctypes.c_uint32 * max(1, nd))()
+        rc = lib().jg_debug_set_read(self.h, int(set_id), ctypes.cast(slots, ctypes.c_void_p), ns,
+                                     ctypes.cast(pool, ctypes.c_void_p), nd)
+        if rc != 0:
+            raise JgError(f"jg_debug_set_read rc={rc}: {self.error()}")
+        return [(slots[2 * k], slots[2 * k + 1]) for k in range(ns)], list(pool[:nd])
+
+    def claims_match_set(self, arena_bytes, jobs, expects, paths, preds, args=None, hargs=None, sets=None, nexpect=None,
+                         null=(), nsets=None):
+        """jg_claims_match_set: claims_match_hash with set predicates.  `preds` may
+        also hold PRED_IN_SET and PRED_ELEMENT_IN_SET (the value is one byte, an
+        index into `sets`); `sets`: the ids of loaded sets the call names, or None
+        for NULL -> (codes: bytes, masks: list of int), both poisoned with 0xee
+        before the call.  `nsets` overrides the count passed to the ABI; `null` as
+        claims_match_hash takes it."""
+        n = len(jobs)
+        es, _keep = _jg_expects(expects)
+        ps, _nkeep = _jg_paths(paths)
+        qs, _vkeep = _jg_preds(preds)
+        ga, _akeep = _jg_args(args, null) if args is not None else (None, None)
+        gh, _hkeep = _jg_hargs(hargs, null) if hargs is not None else (None, None)
+        gs = _jg_setargs(sets, nsets) if sets is not None else None
+        out, masks = _poisoned(ctypes.c_char, n), _poisoned(ctypes.c_uint32, n)
+        self._claims_call("jg_claims_match_set", arena_bytes, _cjobs(jobs), n, es,
+                          len(expects) if nexpect is None else nexpect,
+                          None if "paths" in null else ctypes.byref(ps),
+                          None if "preds" in null else ctypes.byref(qs),
+                          None if ga is None else ctypes.byref(ga),
+                          None if gh is None else ctypes.byref(gh),
+                          None if gs is None else ctypes.byref(gs),
                           None if "codes" in null else out,
                           None if "masks" in null else ctypes.cast(masks, ctypes.c_void_p))
         return out.raw[:n], list(masks[:n])

@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <random>
 #include <stdexcept>
 #include <thread>
 #include <unordered_map>
@@ -1245,6 +1246,18 @@ bool Engine::recover(uint64_t seen) {
       return false;
     }
   }
+  {
+    // the resident sets of the old context, under their ids
+    std::lock_guard<std::mutex> g(set_mu_);
+    for (int id = 0; id < 16; ++id) {
+      if (!sets_[id].live || !sets_[id].stored) continue;
+      if (set_load_locked(id) == 0) continue;
+      lost_ = std::string("jg_set_load: ") + jg_last_error(ctx_);
+      jg_destroy(ctx_);
+      ctx_ = nullptr;
+      return false;
+    }
+  }
   lost_.clear();
   recoveries_.fetch_add(1);
   return true;
@@ -1898,6 +1911,20 @@ const char* claim_code_error(uint8_t code) {
 }
 }  // namespace
 
+// ---- ClaimSet: what a handle shares ----
+using HostSet = std::unordered_set<std::string>;
+struct ClaimSetImpl {
+  Engine* eng = nullptr;
+  int id = -1;
+  uint32_t token = 0;
+  std::mutex mu;                                      // host, host_only, closed
+  std::shared_ptr<const HostSet> host;
+  bool host_only = false, closed = false;
+  ~ClaimSetImpl() {
+    if (!closed && eng && id >= 0) eng->set_release(id);
+  }
+};
+
 namespace {
 // Appends bytes [off, off + len) of the payload that `seg` (canonical unpadded
 // base64url: the scan decided it) encodes, decoding only the characters that
@@ -2028,6 +2055,13 @@ struct MatchPlan {
   jg_hargs hargs{};
   // host path: hosted[i * nhash + c] is what token i's claim must equal under hash column c, "" for none
   mutable std::vector<std::string> hosted;
+  // The resident sets (jg_claims_match_set), with_sets: an InSet or AnyElementIn among the requirements.  The
+  // distinct handles are the call's set indices, at most JG_MAX_SETS of them and none host-only, or the list is
+  // not usable; snaps[k] is the host copy requirement k is held to on the host path, taken when the plan is made.
+  bool with_sets = false;
+  std::vector<std::shared_ptr<ClaimSetImpl>> set_impls;
+  std::vector<std::shared_ptr<const HostSet>> snaps;
+  jg_setargs sets{};
   // token i's operands for the host path
   uint32_t host_bits(const json::Value& claims, size_t i) const;
   // the caller's mask from the scan's
@@ -2134,6 +2168,9 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
   // Both arrays live in one pinned block of the engine's pool (DMA at link
   // speed, no page faults in steady state).
   Engine& eng = ks_->engine();
+  if constexpr (M == kMatchMode)
+    for (const auto& si : match->set_impls)
+      if (si->eng != &eng) throw std::invalid_argument("capjwt: a claim set of another key set");
   const size_t rec_bytes = X ? n * sizeof(jg_claims) : 0;      // jobs | records | selected | masks | codes
   const size_t sel_bytes = X && M >= kSelectMode ? n * sizeof(jg_selected) : 0;
   const size_t mask_bytes = M == kMatchMode ? n * sizeof(uint32_t) : 0;
@@ -2179,7 +2216,7 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
     try {
       const jg_expect& ex = exs[0];
       if constexpr (M == kMatchMode) {
-        if (match->with_hash) {
+        if (match->with_hash || match->with_sets) {
           // a value is hashed with the SHA-2 of its token's alg; a token that is not scanned has no value here
           const size_t nh = match->hargs.nhash;
           if (nh)
@@ -2190,8 +2227,12 @@ void check_core(KeySet* ks_, const std::vector<std::string_view>& tokens, const 
                   if (s.fam) s.fam = (uint8_t)(jobs[i].len ? hash_fam_of_alg(V.toks[i].alg) : 0);
                 }
             });
-          eng.claims_match_hash(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
-                                &match->preds, &match->args, &match->hargs, code, masks, true);
+          if (match->with_sets)
+            eng.claims_match_set(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
+                                 &match->preds, &match->args, &match->hargs, &match->sets, code, masks, true);
+          else
+            eng.claims_match_hash(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
+                                  &match->preds, &match->args, &match->hargs, code, masks, true);
         } else if (match->with_args)
           eng.claims_match_args(V.arena, V.arena_len, jobs, n, exs.data(), (uint32_t)exs.size(), &match->paths,
                                 &match->preds, &match->args, code, masks, true);
@@ -2903,8 +2944,9 @@ void check_requires(const std::vector<Require>& reqs, Require::Op max_op = Requi
 bool scan_byte_ok(unsigned char c) { return c >= 0x20 && c <= 0x7e && c != '"' && c != '\\'; }
 
 // how a requirement's other side travels in jg_preds::values: the text, the column (one byte), or the bound
-std::string pred_value(const Require& r) {
+std::string pred_value(const Require& r, int set_index = 0) {
   switch (r.op) {
+    case Require::InSet: case Require::AnyElementIn: return std::string(1, (char)set_index);
     case Require::Present: case Require::IsString: return std::string();
     case Require::EqualsArg: case Require::AtLeastArg: case Require::AtMostArg: case Require::HashOfArg:
       return std::string(1, (char)r.column);
@@ -2925,7 +2967,28 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vect
                      const std::vector<const int64_t*>& nums_, bool with_args_, const std::vector<HashColumn>* hashes_)
     : reqs(reqs), bit(reqs.size(), -1), with_args(with_args_), strs(&strs_), nums(&nums_), hashes(hashes_) {
   const bool plain = !with_args;                      // MatchBatch's rules: ops 1..4 only
-  check_requires(reqs, plain ? Require::Present : Require::IsString);
+  check_requires(reqs, plain ? Require::Present : Require::AnyElementIn);
+  // the sets: a handle per set requirement, the distinct ones in order of first use are the call's indices
+  std::vector<int> set_index(reqs.size(), 0);
+  snaps.resize(reqs.size());
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    const Require& r = reqs[k];
+    if (r.op < Require::InSet) continue;
+    if (!r.set.impl) throw std::invalid_argument("capjwt: an InSet or AnyElementIn requirement without a claim set");
+    with_sets = true;
+    size_t x = 0;
+    while (x < set_impls.size() && set_impls[x] != r.set.impl) ++x;
+    if (x == set_impls.size()) set_impls.push_back(r.set.impl);
+    set_index[k] = (int)x;
+    std::lock_guard<std::mutex> g(r.set.impl->mu);
+    if (r.set.impl->closed) throw std::invalid_argument("capjwt: the claim set is closed");
+    snaps[k] = r.set.impl->host;
+    if (r.set.impl->host_only) usable = false;
+  }
+  if (set_impls.size() > JG_MAX_SETS) usable = false;
+  if (usable)
+    for (size_t x = 0; x < set_impls.size(); ++x) sets.id[x] = (uint32_t)set_impls[x]->id;
+  sets.nsets = usable ? (uint32_t)set_impls.size() : 0u;
   const size_t nh = hashes ? hashes->size() : 0;
   with_hash = nh > 0;
   for (const Require& r : reqs) {
@@ -2973,7 +3036,9 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vect
     size_t q = 0;
     for (; q < upreds.size(); ++q) {
       const Require& o = reqs[upreds[q]];
-      if (path_of[upreds[q]] == path_of[k] && o.op == r.op && pred_value(o) == pred_value(r)) break;
+      if (path_of[upreds[q]] == path_of[k] && o.op == r.op &&
+          pred_value(o, set_index[upreds[q]]) == pred_value(r, set_index[k]))
+        break;
     }
     if (q == upreds.size()) upreds.push_back(k);
     bit[k] = (int)q;
@@ -2999,7 +3064,7 @@ MatchPlan::MatchPlan(const std::vector<Require>& reqs, size_t n, const std::vect
     const Require& r = reqs[upreds[q]];
     preds.path[q] = (uint8_t)path_of[upreds[q]];
     preds.op[q] = (uint8_t)r.op;
-    const std::string v = pred_value(r);
+    const std::string v = pred_value(r, set_index[upreds[q]]);
     preds.value_len[q] = (uint32_t)v.size();
     values += v;
   }
@@ -3110,8 +3175,10 @@ std::string hash_claim_value(const uint8_t* digest, int fam) {
 namespace {
 // the requirements on a claims map; strs / nums: one token's operands, for the ops that take one
 // hashed: what the token's claim must equal under each hash column, "" for none
+// snaps: per requirement the host copy of its set (InSet, AnyElementIn)
 uint32_t requires_on(const json::Value& all_claims, const std::vector<Require>& reqs, const std::string_view* strs,
-                     const int64_t* nums, const std::string* hashed = nullptr) {
+                     const int64_t* nums, const std::string* hashed = nullptr,
+                     const std::shared_ptr<const HostSet>* snaps = nullptr) {
   uint32_t bits = 0;
   for (size_t k = 0; k < reqs.size(); ++k) {
     const Require& r = reqs[k];
@@ -3155,6 +3222,15 @@ uint32_t requires_on(const json::Value& all_claims, const std::vector<Require>& 
         hit = hashed && !hashed[r.column].empty() && v->kind == json::Value::String && v->str.view() == hashed[r.column];
         break;
       case Require::IsString: hit = v->kind == json::Value::String; break;
+      // s, ok := v.(string); ok && set[s]
+      case Require::InSet:
+        hit = snaps && snaps[k] && v->kind == json::Value::String && snaps[k]->count(std::string(v->str.view())) != 0;
+        break;
+      case Require::AnyElementIn:
+        if (snaps && snaps[k] && v->kind == json::Value::Array)
+          for (const json::Value& e : v->arr)
+            if (e.kind == json::Value::String && snaps[k]->count(std::string(e.str.view())) != 0) { hit = true; break; }
+        break;
     }
     if (hit) bits |= 1u << k;
   }
@@ -3170,11 +3246,11 @@ uint32_t MatchPlan::host_bits(const json::Value& claims, size_t i) const {
     std::vector<int64_t> nv(nums->size());
     for (size_t c = 0; c < sv.size(); ++c) sv[c] = (*strs)[c][i];
     for (size_t c = 0; c < nv.size(); ++c) nv[c] = (*nums)[c][i];
-    return requires_on(claims, reqs, sv.data(), nv.data(), hx);
+    return requires_on(claims, reqs, sv.data(), nv.data(), hx, snaps.data());
   }
   for (size_t c = 0; c < strs->size(); ++c) s[c] = (*strs)[c][i];
   for (size_t c = 0; c < nums->size(); ++c) v[c] = (*nums)[c][i];
-  return requires_on(claims, reqs, s, v, hx);
+  return requires_on(claims, reqs, s, v, hx, snaps.data());
 }
 }  // namespace
 
@@ -3198,18 +3274,25 @@ uint32_t match_requires(const json::Value& all_claims, const std::vector<Require
 uint32_t match_requires(const json::Value& all_claims, const std::vector<Require>& reqs,
                         const std::vector<std::string_view>& strs, const std::vector<int64_t>& nums,
                         const std::vector<std::optional<std::string>>& hashed) {
-  check_requires(reqs, Require::IsString);
-  for (const Require& r : reqs) {
+  check_requires(reqs, Require::AnyElementIn);
+  std::vector<std::shared_ptr<const HostSet>> snaps(reqs.size());
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    const Require& r = reqs[k];
     if (r.op == Require::EqualsArg && r.column >= strs.size())
       throw std::invalid_argument("capjwt: a requirement names a string column that was not given");
     if ((r.op == Require::AtLeastArg || r.op == Require::AtMostArg) && r.column >= nums.size())
       throw std::invalid_argument("capjwt: a requirement names a number column that was not given");
     if (r.op == Require::HashOfArg && r.column >= hashed.size())
       throw std::invalid_argument("capjwt: a requirement names a hash column that was not given");
+    if (r.op >= Require::InSet) {
+      if (!r.set.impl) throw std::invalid_argument("capjwt: an InSet or AnyElementIn requirement without a claim set");
+      std::lock_guard<std::mutex> g(r.set.impl->mu);
+      snaps[k] = r.set.impl->host;
+    }
   }
   std::vector<std::string> hx(hashed.size());
   for (size_t c = 0; c < hashed.size(); ++c) hx[c] = hashed[c] ? *hashed[c] : std::string();
-  return requires_on(all_claims, reqs, strs.data(), nums.data(), hx.data());
+  return requires_on(all_claims, reqs, strs.data(), nums.data(), hx.data(), snaps.data());
 }
 
 std::vector<MatchResult> Validator::MatchBatch(const std::vector<std::string_view>& tokens, const Expected& expected,
@@ -3354,6 +3437,193 @@ __attribute__((weak)) int jg_claims_match_args(jg_ctx*, const uint8_t*, size_t, 
 __attribute__((weak)) int jg_claims_match_hash(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
                                                uint32_t, const jg_paths*, const jg_preds*, const jg_args*, const jg_hargs*,
                                                uint8_t*, uint32_t*);
+// ... and the resident sets with their scan (the MatchArgs entries with InSet or AnyElementIn)
+__attribute__((weak)) int jg_claims_match_set(jg_ctx*, const uint8_t*, size_t, const jg_cjob*, size_t, const jg_expect*,
+                                              uint32_t, const jg_paths*, const jg_preds*, const jg_args*, const jg_hargs*,
+                                              const jg_setargs*, uint8_t*, uint32_t*);
+__attribute__((weak)) int jg_set_load(jg_ctx*, uint32_t, const uint8_t*, size_t, const jg_sarg*, size_t, uint32_t);
+__attribute__((weak)) int jg_set_free(jg_ctx*, uint32_t);
+__attribute__((weak)) int jg_set_info(jg_ctx*, uint32_t, jg_setinfo*);
+}
+
+void Engine::claims_match_set(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs,
+                              const void* expects, uint32_t nexpect, const void* paths, const void* preds,
+                              const void* args, const void* hargs, const void* sets, uint8_t* codes, uint32_t* masks,
+                              bool inside_verify) {
+  abi_call("jg_claims_match_set", jg_claims_match_set != nullptr, inside_verify, [&] {
+    return jg_claims_match_set(ctx_, arena, arena_len, (const jg_cjob*)jobs, njobs, (const jg_expect*)expects, nexpect,
+                               (const jg_paths*)paths, (const jg_preds*)preds, (const jg_args*)args,
+                               (const jg_hargs*)hargs, (const jg_setargs*)sets, codes, masks);
+  });
+}
+
+// ---- resident sets ----
+int Engine::set_acquire() {
+  std::lock_guard<std::mutex> g(set_mu_);
+  for (int id = 0; id < 16; ++id)
+    if (!sets_[id].live) {
+      sets_[id] = SetRecord{};
+      sets_[id].live = true;
+      return id;
+    }
+  throw std::runtime_error("capjwt: 16 claim sets are live on this key set: close one first");
+}
+
+// with set_mu_ held and ctx_ valid; a library without jg_set_load keeps the record only: its scan entry is
+// missing too, and a call that names the set reports the scan as unavailable
+int Engine::set_load_locked(int id) {
+  if (!jg_set_load) return 0;
+  const SetRecord& r = sets_[id];
+  std::vector<jg_sarg> m(r.spans.size());
+  for (size_t k = 0; k < m.size(); ++k) m[k] = jg_sarg{r.spans[k].first, r.spans[k].second};
+  return jg_set_load(ctx_, (uint32_t)id, (const uint8_t*)r.bytes.data(), r.bytes.size(), m.data(), m.size(), r.seed);
+}
+
+void Engine::set_store(int id, const std::vector<std::string>& members, uint32_t seed) {
+  SetRecord n;
+  n.live = n.stored = true;
+  n.seed = seed;
+  for (const std::string& m : members) {
+    n.spans.emplace_back((uint32_t)n.bytes.size(), (uint32_t)m.size());
+    n.bytes += m;
+  }
+  std::shared_lock<std::shared_mutex> life(life_);
+  std::lock_guard<std::mutex> g(set_mu_);
+  if (!ctx_) throw std::runtime_error("capjwt: claim set not loaded: device lost: " + lost_);
+  std::swap(sets_[id], n);
+  const int rc = set_load_locked(id);
+  if (rc != 0) {
+    std::swap(sets_[id], n);                          // what the id held before stays in force, here as on the device
+    throw std::runtime_error(std::string("capjwt: jg_set_load: ") + jg_last_error(ctx_));
+  }
+}
+
+void Engine::set_release(int id) {
+  std::shared_lock<std::shared_mutex> life(life_);
+  std::lock_guard<std::mutex> g(set_mu_);
+  if (id < 0 || id >= 16 || !sets_[id].live) return;
+  if (sets_[id].stored && ctx_ && jg_set_free) (void)jg_set_free(ctx_, (uint32_t)id);
+  sets_[id] = SetRecord{};
+}
+
+Engine::SetInfo Engine::set_info(int id) {
+  std::shared_lock<std::shared_mutex> life(life_);
+  SetInfo out;
+  jg_setinfo i{};
+  if (ctx_ && jg_set_info && jg_set_info(ctx_, (uint32_t)id, &i) == 0)
+    out = SetInfo{i.n, i.nslots, i.maxprobe, i.seed, i.pool_bytes, i.generation};
+  return out;
+}
+
+// ---- ClaimSet ----
+namespace {
+std::mutex g_set_tokens_mu;
+std::unordered_map<uint32_t, std::weak_ptr<ClaimSetImpl>> g_set_tokens;
+uint32_t g_next_set_token = 1;
+
+bool set_member_ok(const std::string& m) {
+  if (m.size() > JG_SET_MEMBER_MAX) return false;
+  for (unsigned char c : m)
+    if (!(c >= 0x20 && c <= 0x7e && c != '"' && c != '\\')) return false;
+  return true;
+}
+uint32_t random_seed() {
+  std::random_device rd;
+  return (uint32_t)rd();
+}
+// the members as both paths take them: the host copy, the distinct ones in order, and whether the device takes all
+void split_members(const std::vector<std::string>& members, std::shared_ptr<HostSet>* host, std::vector<std::string>* distinct,
+                   bool* host_only) {
+  *host = std::make_shared<HostSet>();
+  *host_only = false;
+  for (const std::string& m : members) {
+    if (m.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim set member holds a NUL byte");
+    if (!(*host)->insert(m).second) continue;
+    distinct->push_back(m);
+    if (!set_member_ok(m)) *host_only = true;
+  }
+}
+}  // namespace
+
+void ClaimSet::Replace(const std::vector<std::string>& members, std::optional<uint32_t> seed) {
+  if (!impl) throw std::invalid_argument("capjwt: an empty ClaimSet handle");
+  std::shared_ptr<HostSet> host;
+  std::vector<std::string> distinct;
+  bool host_only = false;
+  split_members(members, &host, &distinct, &host_only);
+  std::lock_guard<std::mutex> g(impl->mu);
+  if (impl->closed) throw std::invalid_argument("capjwt: the claim set is closed");
+  // a host-only set keeps its id with nothing in it: a scan that captured the id before sees a set, never a hole
+  impl->eng->set_store(impl->id, host_only ? std::vector<std::string>() : distinct, seed ? *seed : random_seed());
+  impl->host = std::move(host);
+  impl->host_only = host_only;
+}
+
+void ClaimSet::Close() {
+  if (!impl) return;
+  std::lock_guard<std::mutex> g(impl->mu);
+  if (impl->closed) return;
+  impl->closed = true;
+  impl->eng->set_release(impl->id);
+}
+
+size_t ClaimSet::size() const {
+  if (!impl) return 0;
+  std::lock_guard<std::mutex> g(impl->mu);
+  return impl->host ? impl->host->size() : 0;
+}
+
+ClaimSet::Info ClaimSet::info() const {
+  Info out;
+  if (!impl) return out;
+  std::lock_guard<std::mutex> g(impl->mu);
+  out.n = impl->host ? impl->host->size() : 0;
+  out.host_only = impl->host_only;
+  if (!impl->closed && !impl->host_only) {
+    const Engine::SetInfo i = impl->eng->set_info(impl->id);
+    out.nslots = i.nslots;
+    out.maxprobe = i.maxprobe;
+    out.seed = i.seed;
+    out.pool_bytes = i.pool_bytes;
+    out.generation = i.generation;
+  }
+  return out;
+}
+
+uint32_t ClaimSet::token() const { return impl ? impl->token : 0; }
+
+ClaimSet ClaimSet::from_token(uint32_t token) {
+  ClaimSet s;
+  std::lock_guard<std::mutex> g(g_set_tokens_mu);
+  auto it = g_set_tokens.find(token);
+  if (it != g_set_tokens.end()) s.impl = it->second.lock();
+  return s;
+}
+
+ClaimSet Validator::NewClaimSet(const std::vector<std::string>& members, std::optional<uint32_t> seed) {
+  std::shared_ptr<HostSet> host;
+  std::vector<std::string> distinct;
+  bool host_only = false;
+  split_members(members, &host, &distinct, &host_only);   // throws before an id is taken
+  Engine& eng = ks_->engine();
+  ClaimSet s;
+  s.impl = std::make_shared<ClaimSetImpl>();
+  s.impl->eng = &eng;
+  s.impl->id = eng.set_acquire();
+  try {
+    eng.set_store(s.impl->id, host_only ? std::vector<std::string>() : distinct, seed ? *seed : random_seed());
+  } catch (...) {
+    eng.set_release(s.impl->id);
+    s.impl->id = -1;
+    throw;
+  }
+  s.impl->host = std::move(host);
+  s.impl->host_only = host_only;
+  std::lock_guard<std::mutex> g(g_set_tokens_mu);
+  for (auto it = g_set_tokens.begin(); it != g_set_tokens.end();) it = it->second.expired() ? g_set_tokens.erase(it) : std::next(it);
+  s.impl->token = g_next_set_token++;
+  g_set_tokens[s.impl->token] = s.impl;
+  return s;
 }
 
 void Engine::claims_scan(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expect,

@@ -38,6 +38,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "jose.hpp"
@@ -227,6 +228,23 @@ class Engine {
   void claims_match_hash(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
                          uint32_t nexpect, const void* paths, const void* preds, const void* args, const void* hargs,
                          uint8_t* codes, uint32_t* masks, bool inside_verify = false);
+  // ... and with resident sets (`sets`, a jg_setargs) for InSet / AnyElementIn (jg_claims_match_set)
+  void claims_match_set(const uint8_t* arena, size_t arena_len, const void* jobs, size_t njobs, const void* expects,
+                        uint32_t nexpect, const void* paths, const void* preds, const void* args, const void* hargs,
+                        const void* sets, uint8_t* codes, uint32_t* masks, bool inside_verify = false);
+  // Resident sets (jg_set_load / jg_set_free / jg_set_info), ids 0..15 of the
+  // context.  set_acquire() hands out a free id or throws for the 17th live set;
+  // set_store() loads `members` (device-legal, distinct) under `seed` and keeps
+  // them, so that recover() can load the set again into a new context; a failure
+  // throws and leaves what the id held before.  set_release() frees the id.
+  struct SetInfo {
+    uint32_t n = 0, nslots = 0, maxprobe = 0, seed = 0;
+    uint64_t pool_bytes = 0, generation = 0;
+  };
+  int set_acquire();
+  void set_store(int id, const std::vector<std::string>& members, uint32_t seed);
+  void set_release(int id);
+  SetInfo set_info(int id);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
   // of blocks the engine keeps; back to the pool when the Pinned dies.
   class Pinned {
@@ -267,6 +285,15 @@ class Engine {
   std::shared_mutex life_;        // shared: calls on ctx_; unique: recover (ctx_ replaced)
   std::mutex load_mu_;            // serialises loads; guards keys_
   std::vector<PublicKey> keys_;   // the list the context holds (re-staged by recover)
+  struct SetRecord {              // a live id: what it holds (loaded again by recover), under set_mu_
+    bool live = false, stored = false;
+    std::string bytes;
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    uint32_t seed = 0;
+  };
+  std::mutex set_mu_;
+  SetRecord sets_[16];
+  int set_load_locked(int id);    // jg_set_load of sets_[id] into ctx_: its return code
   bool has_keys_ = false;
   std::atomic<uint64_t> errors_{0};
   uint64_t recovered_at_ = 0;     // errors_ when the last recovery ran (under life_)
@@ -512,6 +539,39 @@ using ClaimPath = std::vector<std::string>;
 struct ClaimPaths {
   std::vector<ClaimPath> paths;
 };
+// A set of strings a claim can be held against (InSet, AnyElementIn): a deny-list
+// of revoked ids, the tenants a gateway serves.  Made by Validator::NewClaimSet
+// from the key set that owns the device context; a shared handle that owns one
+// of the context's 16 set ids and frees it when the last copy dies (or at
+// Close()).  It must not outlive that key set.  The members are any strings
+// without a NUL (std::invalid_argument otherwise); a host copy answers the host
+// path.  A set all of whose members the device takes -- at most 255 bytes, each
+// printable ASCII without quote and backslash -- is resident on the device;
+// any other set is host-only (Info().host_only) and every token of a call that
+// names it is answered from the host path, so no result depends on it.
+struct ClaimSetImpl;
+class ClaimSet {
+ public:
+  struct Info {
+    size_t n = 0;                   // distinct members
+    bool host_only = false;
+    uint32_t nslots = 0, maxprobe = 0, seed = 0;   // of the resident table (0 for a host-only set)
+    uint64_t pool_bytes = 0, generation = 0;
+  };
+  ClaimSet() = default;
+  explicit operator bool() const { return (bool)impl; }
+  size_t size() const;
+  Info info() const;
+  // The whole set anew, under the same id.  Any failure (a NUL: invalid_argument;
+  // a device allocation or load failure: runtime_error) leaves the old members in
+  // force on both paths.  seed: random per load unless given (tests).
+  void Replace(const std::vector<std::string>& members, std::optional<uint32_t> seed = std::nullopt);
+  void Close();                     // frees the id now; a later call that names the set throws
+  uint32_t token() const;           // a process-wide number of this handle, for bindings: from_token() finds it again
+  static ClaimSet from_token(uint32_t token);
+  std::shared_ptr<ClaimSetImpl> impl;
+};
+
 // A yes/no question about one claim (MatchBatch).  With v the value the claims
 // map holds at `path`:
 //   Equals      v is a string equal to `value` ("" allowed)
@@ -535,18 +595,25 @@ struct ClaimPaths {
 // Go's (verified, err) of IDToken.VerifyAccessToken is (IsString & HashOfArg,
 // err != nil exactly when IsString holds, HashOfArg does not and the alg is not
 // EdDSA).
+// ... and, for the same entries, membership in a ClaimSet (jg_claims_match_set):
+//   InSet         v is a string equal to a member of `set`
+//   AnyElementIn  v is an array and one of its direct elements is a string equal
+//                 to a member of `set` (HasElement's rules)
+// At most 4 distinct resident sets are scanned per call; a call that names more,
+// or a host-only set, is answered from the host path for every token.
 // The numbers are jg_pred_op's (include/jg.h).
 struct Require {
   enum Op : uint8_t {
     Equals = 1, HasWord = 2, HasElement = 3, Present = 4,
     EqualsArg = 5, AtLeast = 6, AtMost = 7, AtLeastArg = 8, AtMostArg = 9,
-    HashOfArg = 10, IsString = 11
+    HashOfArg = 10, IsString = 11, InSet = 12, AnyElementIn = 13
   };
   ClaimPath path;
   Op op = Present;
   std::string value;
   int64_t bound = 0;
   uint32_t column = 0;
+  ClaimSet set{};                   // InSet, AnyElementIn
 };
 // One hash column of a MatchBatchArgs call: per token the value to hash (an
 // access token, an authorization code: any bytes), or nothing
@@ -581,6 +648,10 @@ struct SelectColumns {
 class Validator {
  public:
   explicit Validator(KeySet* ks) : ks_(ks) {}
+  // A ClaimSet on this validator's key set (its device context).  Throws
+  // std::invalid_argument for a NUL in a member and std::runtime_error for a 17th
+  // live set or a failed load.  seed: random unless given (tests).
+  ClaimSet NewClaimSet(const std::vector<std::string>& members, std::optional<uint32_t> seed = std::nullopt);
   Result Validate(std::string_view token, const Expected& expected);
   Results ValidateBatch(const std::vector<std::string_view>& tokens, const Expected& expected);
   // Verdict-only ValidateBatch: out[i] is Validate(tokens[i], expected)'s (ok,

@@ -782,10 +782,41 @@ PYBIND11_MODULE(_capjwt_host, m) {
   auto arg_requires_of = [](const ArgReqList& reqs) {
     std::vector<Require> rq;
     rq.reserve(reqs.size());
-    for (const auto& [path, op, value, bound, column] : reqs)
+    for (const auto& [path, op, value, bound, column] : reqs) {
       rq.push_back(Require{path, (Require::Op)op, value, bound, column});
+      // InSet / AnyElementIn: the column is the handle's token (ClaimSet.token)
+      if (op == Require::InSet || op == Require::AnyElementIn) {
+        rq.back().set = ClaimSet::from_token(column);
+        if (!rq.back().set) throw py::value_error("capjwt: the claim set of a requirement is gone");
+        rq.back().column = 0;
+      }
+    }
     return rq;
   };
+  struct PyClaimSet {
+    std::shared_ptr<KeySet> ks;     // the context the set lives in
+    ClaimSet set;
+  };
+  py::class_<PyClaimSet>(m, "ClaimSet")
+      .def("replace", [](PyClaimSet& s, const std::vector<std::string>& members, std::optional<uint32_t> seed) {
+        py::gil_scoped_release rel;
+        s.set.Replace(members, seed);
+      }, py::arg("members"), py::arg("seed") = py::none())
+      .def("close", [](PyClaimSet& s) { s.set.Close(); })
+      .def("token", [](PyClaimSet& s) { return s.set.token(); })
+      .def("__len__", [](PyClaimSet& s) { return s.set.size(); })
+      .def("info", [](PyClaimSet& s) {
+        const ClaimSet::Info i = s.set.info();
+        py::dict d;
+        d["n"] = i.n;
+        d["host_only"] = i.host_only;
+        d["nslots"] = i.nslots;
+        d["maxprobe"] = i.maxprobe;
+        d["seed"] = i.seed;
+        d["pool_bytes"] = i.pool_bytes;
+        d["generation"] = i.generation;
+        return d;
+      });
   // the number columns of a call: the buffers stay requested (and so alive) for its duration
   struct NumCols {
     std::vector<py::buffer_info> infos;
@@ -898,6 +929,13 @@ PYBIND11_MODULE(_capjwt_host, m) {
         p->v = std::make_unique<Validator>(ks->ks.get());
         return p;
       }))
+      .def("new_claim_set", [](PyValidator& s, const std::vector<std::string>& members, std::optional<uint32_t> seed) {
+        auto p = std::make_unique<PyClaimSet>();
+        p->ks = s.ks;
+        py::gil_scoped_release rel;
+        p->set = s.v->NewClaimSet(members, seed);
+        return p;
+      }, py::arg("members"), py::arg("seed") = py::none())
       .def("validate", [](PyValidator& s, py::object tok, const Expected& e) {
         std::string t = tok.cast<std::string>();
         Result r;

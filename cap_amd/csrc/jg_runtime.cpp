@@ -49,6 +49,7 @@
 #include "kernels/common.hpp"
 #include "kernels/ecdsa.hpp"
 #include "kernels/ed25519.hpp"
+#include "kernels/claim_set_build.hpp"
 #include "kernels/claims.hpp"
 #include "kernels/hash.hpp"
 #include "kernels/hash_operand.hpp"
@@ -723,6 +724,7 @@ struct Device {
   Grow cl_preds, cl_match;          // jg_claims_match's resolved predicates and its masks
   Grow cl_abytes, cl_astr, cl_anum; // jg_claims_match_args' operands: the bytes, the span table, the numbers
   Grow cl_hbytes, cl_hsrc;          // jg_claims_match_hash's sources: the bytes to hash, the source table
+  hipStream_t setstream = nullptr;  // jg_set_load's uploads (devs[0] only): beside the scans, never on their stream
   uint32_t* gtab[NCLS] = {};
   uint32_t* btab = nullptr;
   std::shared_ptr<SharedTable> tab_ref[NCLS];   // keeps gtab / btab alive
@@ -747,6 +749,16 @@ struct Device {
   std::deque<Slot*> cq;            // in-flight chunks, enqueue order
   bool cstop = false;
 };
+
+// One loaded set (jg_set_load): the table and the pool on the first device, and
+// what jg_set_info reports.  Immutable once published; a scan holds the sets it
+// names until it has ended, so the memory outlives a replacement or a free.
+struct LoadedSet {
+  DevBufP slots, pool;
+  uint32_t n = 0, nslots = 0, maxprobe = 0, seed = 0;
+  uint64_t pool_bytes = 0, generation = 0;
+};
+using LoadedSetP = std::shared_ptr<const LoadedSet>;
 
 }  // namespace
 
@@ -817,6 +829,19 @@ struct jg_ctx {
     // `old` (and, if nothing else holds it, its device memory) dies here, outside the lock
   }
   std::mutex load_mu;             // serialises key loads and upgrade publications
+  // the published sets (jg_set_load): each swapped whole under set_mu; loads are serialised by set_load_mu
+  std::mutex set_mu, set_load_mu;
+  LoadedSetP sets[JG_MAX_LOADED_SETS];
+  uint64_t set_generation = 0;
+  LoadedSetP set_at(uint32_t id) {
+    std::lock_guard<std::mutex> g(set_mu);
+    return id < JG_MAX_LOADED_SETS ? sets[id] : nullptr;
+  }
+  LoadedSetP set_swap(uint32_t id, LoadedSetP n) {     // the old one dies with the caller's copy, outside the lock
+    std::lock_guard<std::mutex> g(set_mu);
+    std::swap(sets[id], n);
+    return n;
+  }
   // background widening of comb tables (narrow table first, wide one swapped in)
   std::thread upgrader;
   std::mutex up_mu;
@@ -2923,6 +2948,7 @@ jg_ctx* jg_create(const int* devices, int ndev) {
       HIPCHK(hipStreamCreateWithFlags(&d->kstream, hipStreamNonBlocking));
       HIPCHK(hipStreamCreateWithFlags(&d->ustream, hipStreamNonBlocking));
       HIPCHK(hipStreamCreateWithFlags(&d->clstream, hipStreamNonBlocking));
+      HIPCHK(hipStreamCreateWithFlags(&d->setstream, hipStreamNonBlocking));
       ctx->devs.push_back(std::move(d));
     }
     auto ks = std::make_shared<KeyState>();        // no keys yet: every job is out of range
@@ -2966,6 +2992,7 @@ void jg_destroy(jg_ctx* ctx) {
     d->planner.reset();
   }
   ctx->publish(nullptr);                           // key generations: handed to the reaper
+  for (uint32_t id = 0; id < JG_MAX_LOADED_SETS; ++id) ctx->set_swap(id, nullptr);   // ... and the sets
   reaper().drain();                                // ... and freed before jg_destroy returns
   for (auto& d : ctx->devs) {
     (void)hipSetDevice(d->id);
@@ -2985,7 +3012,7 @@ void jg_destroy(jg_ctx* ctx) {
       (void)hipStreamSynchronize(d->copy);
       (void)hipStreamDestroy(d->copy);
     }
-    for (hipStream_t* st : {&d->kstream, &d->ustream, &d->clstream})
+    for (hipStream_t* st : {&d->kstream, &d->ustream, &d->clstream, &d->setstream})
       if (*st) {
         (void)hipStreamSynchronize(*st);
         (void)hipStreamDestroy(*st);
@@ -3472,7 +3499,7 @@ int jg_hash_batch(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
 
 namespace {
 
-// One scan of the claims: what the eight jg_claims_* entries hand to claims_run.
+// One scan of the claims: what the nine jg_claims_* entries hand to claims_run.
 // The resolved sides are host objects that `resolve` fills and points these at;
 // each is uploaded into the kept device buffer of its kind, and the kernel is
 // picked from which of them, and which outputs, are there (launch_claims).
@@ -3493,6 +3520,7 @@ struct ClaimsCall {
   const jgclaims::ArgPreds* apreds = nullptr;   // in the place of preds, with args: the jobs' own operands
   const jg_args* args = nullptr;                // NULL with apreds: no plain columns
   const jg_hargs* hargs = nullptr;              // with apreds: the sources of the hashed string columns, behind args' own
+  const jgclaims::SetArgPreds* spreds = nullptr; // apreds is its base: the list names a set op, the headers are filled
 };
 
 const char kRefuseExpect[] = "more than 16 audiences, expected strings over 4096 bytes, or now_nsec >= 1e9";
@@ -3523,6 +3551,13 @@ const char kRefuseHashPreds[] =
     "over 64 bytes, empty for HAS_WORD or HAS_ELEMENT, not empty for PRESENT or IS_STRING or not printable "
     "ASCII without quote and backslash, a space in a HAS_WORD value, more than 4 string or number "
     "columns, a column or hash column index that is not one byte below its count, a bound that is not "
+    "8 bytes, or two identical predicates";
+
+const char kRefuseSetPreds[] =
+    "more than 16 predicates, a path index past the paths, an op outside 1..13, a value that is "
+    "over 64 bytes, empty for HAS_WORD or HAS_ELEMENT, not empty for PRESENT or IS_STRING or not printable "
+    "ASCII without quote and backslash, a space in a HAS_WORD value, more than 4 string or number "
+    "columns, a column, hash column or set index that is not one byte below its count, a bound that is not "
     "8 bytes, or two identical predicates";
 
 // The one path of a scan, after the entry's own NULL-argument test.  `resolve`
@@ -3575,7 +3610,8 @@ int claims_run(jg_ctx* ctx, const std::string& entry, ClaimsCall& c, const std::
     if (c.vals_out) L.vals_out = (jg_claims*)d->cl_vals.get(sizeof(jg_claims) * njobs);
     if (c.sel_out) L.sel_out = (jg_selected*)d->cl_sel.get(sizeof(jg_selected) * njobs);
     if (c.match_out) {
-      if (c.apreds) L.apreds = (const jgclaims::ArgPreds*)upload(d->cl_preds, c.apreds, sizeof *c.apreds);
+      if (c.spreds) L.spreds = (const jgclaims::SetArgPreds*)upload(d->cl_preds, c.spreds, sizeof *c.spreds);
+      else if (c.apreds) L.apreds = (const jgclaims::ArgPreds*)upload(d->cl_preds, c.apreds, sizeof *c.apreds);
       else L.preds = (const jgclaims::Preds*)upload(d->cl_preds, c.preds, sizeof *c.preds);
       L.match_out = (uint32_t*)d->cl_match.get(sizeof(uint32_t) * njobs);
     }
@@ -3831,6 +3867,177 @@ int jg_claims_match_hash(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
     c.match_out = match_out;
     return nullptr;
   });
+}
+
+// jg_claims_match_hash whose list may ask resident sets: the named sets are
+// captured here, for the length of the call, and their headers go up with the
+// resolved predicates (one upload, 184 bytes longer).  A list without a set op
+// is jg_claims_match_hash's call, kernel and all.
+int jg_claims_match_set(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                        const jg_cjob* jobs, size_t njobs, const jg_expect* expects, uint32_t nexpect,
+                        const jg_paths* paths, const jg_preds* preds, const jg_args* args, const jg_hargs* hargs,
+                        const jg_setargs* sets, uint8_t* code_out, uint32_t* match_out) {
+  if (!ctx || !expects || (njobs > 0 && (!jobs || !code_out || !paths || !preds || !match_out)) ||
+      (arena_len > 0 && !arena))
+    return -1;
+  ClaimsCall c{arena, arena_len, jobs, njobs, code_out, nullptr, nullptr};
+  auto T = std::make_unique<jgclaims::Profiles>();
+  auto P = std::make_unique<jgclaims::Paths>();
+  auto Q = std::make_unique<jgclaims::SetArgPreds>();
+  LoadedSetP held[JG_MAX_SETS];
+  std::string why;
+  return claims_run(ctx, "jg_claims_match_set", c, [&]() -> const char* {
+    const uint32_t nstr = args ? args->nstr : 0u, nnum = args ? args->nnum : 0u, nhash = hargs ? hargs->nhash : 0u;
+    const uint32_t nsets = sets ? sets->nsets : 0u;
+    if (!jgclaims::resolve_profiles(expects, nexpect, T.get())) return kRefuseProfiles;
+    if (!jgclaims::resolve_paths(*paths, P.get())) return kRefusePaths;
+    if (nhash > JG_MAX_HASH_ARGS || (nstr <= JG_MAX_ARGS && nstr + nhash > JG_MAX_ARGS))
+      return "more than 2 hash columns, or more than 4 string and hash columns together";
+    if (nsets > JG_MAX_SETS) return "more than 4 sets";
+    for (uint32_t x = 0; x < nsets; ++x) {
+      held[x] = ctx->set_at(sets->id[x]);
+      if (held[x]) continue;
+      why = "set index " + std::to_string(x) + " names id " + std::to_string(sets->id[x]) + ", which is 16 or more or not loaded";
+      return why.c_str();
+    }
+    if (!jgclaims::resolve_arg_preds(*preds, *P, nstr, nnum, Q.get(), true, nhash, nsets, &Q->sets)) return kRefuseSetPreds;
+    if (args && ((args->bytes_len && !args->bytes) || (nstr && !args->str) || (nnum && !args->num)))
+      return "the operands' bytes, spans or numbers are NULL";
+    if (hargs && ((hargs->bytes_len && !hargs->bytes) || (nhash && !hargs->src)))
+      return "the hash sources' bytes or table are NULL";
+    if (hargs && hargs->bytes_len >= (uint64_t(1) << 32) - ARENA_SLACK) return "the hash sources' bytes pass 4 GiB";
+    if ((args ? args->bytes_len : 0) + 4 + (uint64_t)njobs * nhash * jghop::kSlot >= (uint64_t(1) << 32) - ARENA_SLACK)
+      return "the operand bytes with the hashed columns pass 4 GiB";
+    for (size_t i = 0; i < njobs; ++i) {
+      if (args && !jgclaims::arg_operands_ok(*args, i)) {
+        why = "job " + std::to_string(i) + " has a string operand over 64 bytes, past the operand bytes or "
+              "with a byte that is not printable ASCII without quote and backslash";
+        return why.c_str();
+      }
+      if (nhash && !jgclaims::hash_sources_ok(*hargs, i)) {
+        why = "job " + std::to_string(i) + " has a hash source over 8192 bytes, past the source bytes or "
+              "with a family outside 0..3";
+        return why.c_str();
+      }
+    }
+    bool setop = false;
+    for (uint32_t k = 0; k < JG_MAX_PATHS; ++k) setop = setop || Q->sets.inset[k] || Q->sets.elemset[k];
+    for (uint32_t x = 0; x < nsets; ++x) {
+      jgclaims::SetHeader& H = Q->sets.h[x];
+      H.slots = (uint64_t)(uintptr_t)held[x]->slots->p;
+      H.pool = (uint64_t)(uintptr_t)held[x]->pool->p;
+      H.mask = held[x]->nslots - 1u;
+      H.maxprobe = held[x]->maxprobe;
+      H.seed = held[x]->seed;
+      H.n = held[x]->n;
+    }
+    c.table = T.get();
+    c.paths = P.get();
+    c.apreds = Q.get();
+    c.spreds = setop ? Q.get() : nullptr;
+    c.args = args;
+    c.hargs = nhash ? hargs : nullptr;
+    c.match_out = match_out;
+    return nullptr;
+  });
+}
+
+// Builds on the host, uploads on the set stream of the first device, publishes.
+// Nothing is published before the upload has completed, and every failure
+// returns before the swap: the id keeps naming what it named.
+int jg_set_load(jg_ctx* ctx, uint32_t id, const uint8_t* bytes, size_t bytes_len,
+                const jg_sarg* members, size_t n, uint32_t seed) {
+  if (!ctx) return -1;
+  if (id >= JG_MAX_LOADED_SETS || (n > 0 && !members) || (bytes_len > 0 && !bytes)) {
+    ctx->set_err("jg_set_load: an id of 16 or more, or members or bytes NULL");
+    return -1;
+  }
+  jgset::Built B;
+  size_t bad = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = jgset::set_build(bytes, bytes_len, members, n, seed, &B, &bad);
+  const auto t1 = std::chrono::steady_clock::now();
+  if (rc == -1) {
+    ctx->set_err("jg_set_load: member " + std::to_string(bad) + " is past the bytes, over 255 bytes or holds a byte "
+                 "that is not printable ASCII without quote and backslash");
+    return -1;
+  }
+  if (rc != 0) {
+    ctx->set_err("jg_set_load: more than 2^24 distinct members, or their lengths and bytes come to 4 GiB or more");
+    return -1;
+  }
+  try {
+    Device* d = ctx->devs[0].get();
+    std::lock_guard<std::mutex> g(ctx->set_load_mu);
+    auto S = std::make_shared<LoadedSet>();
+    const size_t sbytes = sizeof(jgset::Slot) * B.slots.size(), pbytes = 4 * B.pool.size();
+    S->slots = dev_alloc(d->id, sbytes, &ctx->fail_alloc);
+    S->pool = dev_alloc(d->id, pbytes + ARENA_SLACK, &ctx->fail_alloc);
+    HIPCHK(hipSetDevice(d->id));
+    const hipStream_t s = d->setstream;
+    HIPCHK(hipMemcpyAsync(S->slots->p, B.slots.data(), sbytes, hipMemcpyHostToDevice, s));
+    if (pbytes) HIPCHK(hipMemcpyAsync(S->pool->p, B.pool.data(), pbytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync((uint8_t*)S->pool->p + pbytes, 0, ARENA_SLACK, s));
+    HIPCHK(hipStreamSynchronize(s));
+    S->n = B.n;
+    S->nslots = (uint32_t)B.slots.size();
+    S->maxprobe = B.maxprobe;
+    S->seed = seed;
+    S->pool_bytes = pbytes;
+    S->generation = ++ctx->set_generation;
+    ctx->set_swap(id, std::move(S));
+    if (load_trace()) {                                 // CAPJWT_LOAD_TRACE=1, as jg_keys_load's phases
+      const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+      std::fprintf(stderr, "[capjwt] jg_set_load id %u: %u members, build %.1f ms, alloc + upload %.1f ms\n", id, B.n, ms(t0, t1),
+                   ms(t1, std::chrono::steady_clock::now()));
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(std::string("jg_set_load: ") + e.what());
+    return -2;
+  }
+}
+
+int jg_set_free(jg_ctx* ctx, uint32_t id) {
+  if (!ctx) return -1;
+  if (id >= JG_MAX_LOADED_SETS || !ctx->set_swap(id, nullptr)) {
+    ctx->set_err("jg_set_free: an id of 16 or more, or not loaded");
+    return -1;
+  }
+  return 0;
+}
+
+int jg_set_info(jg_ctx* ctx, uint32_t id, jg_setinfo* out) {
+  if (!ctx) return -1;
+  const LoadedSetP S = ctx->set_at(id);
+  if (!S || !out) {
+    ctx->set_err("jg_set_info: an id of 16 or more or not loaded, or out NULL");
+    return -1;
+  }
+  *out = jg_setinfo{S->n, S->nslots, S->maxprobe, S->seed, S->pool_bytes, S->generation};
+  return 0;
+}
+
+// The set's table and pool as they lie on the device, for the tests that compare
+// them with their model: up to cap_slots slots (hash, ref pairs) and cap_pool
+// dwords.  -1: not loaded, or a cap below the set's size.
+int jg_debug_set_read(jg_ctx* ctx, uint32_t id, uint32_t* slots_out, size_t cap_slots, uint32_t* pool_out, size_t cap_pool) {
+  if (!ctx) return -1;
+  const LoadedSetP S = ctx->set_at(id);
+  if (!S || cap_slots < S->nslots || cap_pool < S->pool_bytes / 4 || !slots_out || (S->pool_bytes && !pool_out)) {
+    ctx->set_err("jg_debug_set_read: not loaded, or an output too small");
+    return -1;
+  }
+  try {
+    // plain blocking copies of a set this call holds: no stream of the runtime's and no lock, so loads go on beside it
+    HIPCHK(hipSetDevice(ctx->devs[0]->id));
+    HIPCHK(hipMemcpy(slots_out, S->slots->p, sizeof(jgset::Slot) * S->nslots, hipMemcpyDeviceToHost));
+    if (S->pool_bytes) HIPCHK(hipMemcpy(pool_out, S->pool->p, S->pool_bytes, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (const std::exception& e) {
+    ctx->set_err(std::string("jg_debug_set_read: ") + e.what());
+    return -2;
+  }
 }
 
 const char* jg_last_error(jg_ctx* ctx) {

@@ -53,6 +53,17 @@ struct ArgSrc {
   __device__ __forceinline__ int64_t bound(uint32_t c) const { return num[c]; }
 };
 
+// ArgSrc for jg_claims_match_set: the lane's segment too, read again by group in
+// any order (WordSrc::word goes forward only), for the compare that confirms a
+// set hit.  The same two aligned words per group, so the same seven bytes of slack.
+struct SetArgSrc : ArgSrc {
+  const uint32_t* aligned;
+  uint32_t shift8;
+  __device__ __forceinline__ uint32_t peek(uint32_t g) const {
+    return (uint32_t)((((uint64_t)aligned[g + 1] << 32) | aligned[g]) >> shift8);
+  }
+};
+
 constexpr int kBlock = 256;
 
 // the block copies `words` 32-bit words of *src, from word `first` on, to its LDS object *dst
@@ -82,7 +93,7 @@ __device__ __forceinline__ void store_selected(jg_selected* out, const jg_select
                     q.type[4] | (uint32_t)q.type[5] << 8 | (uint32_t)q.type[6] << 16 | (uint32_t)q.type[7] << 24, 0u, 0u);
 }
 
-// The body of all nine kernels.  M is the scan's mode.  X is the block's LDS
+// The body of all ten kernels.  M is the scan's mode.  X is the block's LDS
 // copy of the expected side, XS its type:
 //   Expect    one for the call, copied whole;
 //   Profiles  the call's table (jg_claims_each), copied only as far as it is in
@@ -96,7 +107,9 @@ __device__ __forceinline__ void store_selected(jg_selected* out, const jg_select
 // and constant indices only) until they are stored.  Q is the LDS copy of the
 // predicates of kMatch and kMatchArgs (PQ: Preds or ArgPreds), which keep no
 // record: a byte and a dword per lane.  kMatchArgs also reads the lane's own
-// operands, from global memory (ArgSrc).
+// operands, from global memory (ArgSrc).  kMatchSet is kMatchArgs with SetArgPreds
+// for PQ: the tables of the call's sets are read from global memory through the
+// addresses its headers hold, and the segment a second time (SetArgSrc).
 template <int M, class XS, class SL, class PQ = Preds>
 __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restrict__ arena,
                                             const jg_cjob* __restrict__ jobs, int64_t n, const XS* __restrict__ expect,
@@ -135,7 +148,11 @@ __device__ __forceinline__ void claims_body(XS& X, SL* S, const uint8_t* __restr
   jg_claims v;
   jg_selected q;
   uint32_t bits;
-  if constexpr (M == kMatchArgs) {
+  if constexpr (M == kMatchSet) {
+    const ProfileRef E{X, J.flags < np ? J.flags : 0u};
+    const SetArgSrc A{{(const uint32_t*)arg_bytes, arg_str + i * nstr, arg_num + i * nnum, nstr}, src.aligned, src.shift8};
+    code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q, Q, &bits, &A);
+  } else if constexpr (M == kMatchArgs) {
     const ProfileRef E{X, J.flags < np ? J.flags : 0u};
     const ArgSrc A{(const uint32_t*)arg_bytes, arg_str + i * nstr, arg_num + i * nnum, nstr};
     code_out[i] = scan_segment<M>(src, J.len, E, &v, S, &q, Q, &bits, &A);
@@ -273,6 +290,26 @@ __global__ void __launch_bounds__(kBlock) k_claims_match_args(const uint8_t* __r
                                                      preds, match_out, arg_bytes, arg_str, arg_num, nstr, nnum);
 }
 
+// k_claims_match_args whose predicates may also ask whether a string is a member
+// of a resident set (jg_claims_match_set): SetArgPreds sits in LDS in the place
+// of ArgPreds, with the headers of the call's sets behind the predicates.
+__global__ void __launch_bounds__(kBlock) k_claims_match_set(const uint8_t* __restrict__ arena,
+                                                             const jg_cjob* __restrict__ jobs, int64_t n,
+                                                             const Profiles* __restrict__ table,
+                                                             const Paths* __restrict__ paths,
+                                                             const SetArgPreds* __restrict__ preds,
+                                                             const uint8_t* __restrict__ arg_bytes,
+                                                             const jg_sarg* __restrict__ arg_str,
+                                                             const int64_t* __restrict__ arg_num, uint32_t nstr,
+                                                             uint32_t nnum, uint8_t* __restrict__ code_out,
+                                                             uint32_t* __restrict__ match_out) {
+  __shared__ Profiles T;
+  __shared__ Paths P;
+  __shared__ SetArgPreds Q;
+  claims_body<kMatchSet, Profiles, Paths, SetArgPreds>(T, &P, arena, jobs, n, table, paths, code_out, nullptr, nullptr,
+                                                       &Q, preds, match_out, arg_bytes, arg_str, arg_num, nstr, nnum);
+}
+
 }  // namespace
 
 void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
@@ -281,7 +318,10 @@ void launch_claims(const ClaimsLaunch& c, hipStream_t s) {
   const auto go = [&](auto kernel, auto... rest) {
     hipLaunchKernelGGL(kernel, grid, block, 0, s, c.arena, c.jobs, c.n, rest...);
   };
-  if (c.apreds)
+  if (c.spreds)
+    go(k_claims_match_set, c.table, c.paths, c.spreds, c.arg_bytes, c.arg_str, c.arg_num, c.nstr, c.nnum, c.code_out,
+       c.match_out);
+  else if (c.apreds)
     go(k_claims_match_args, c.table, c.paths, c.apreds, c.arg_bytes, c.arg_str, c.arg_num, c.nstr, c.nnum, c.code_out,
        c.match_out);
   else if (c.match_out) go(k_claims_match_each, c.table, c.paths, c.preds, c.code_out, c.match_out);

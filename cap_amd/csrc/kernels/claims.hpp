@@ -54,6 +54,14 @@
 // EQUALS_ARG on a string column whose operand k_hash_operand wrote
 // (hash_operand.hpp), so the scan itself knows nothing about hashes.
 //
+// claims_match_set() is a seventh mode (ScanT<kMatchSet>): kMatchArgs whose
+// predicates (SetArgPreds: ArgPreds and, behind it, SetPreds) may also ask whether
+// a string, or a string element of an array, is a member of a resident set
+// (claim_set.hpp): the string is hashed as it goes by -- one running hash, seeded
+// per set only where it is finalised -- and looked up at its closing quote; a slot
+// whose hash and length agree is confirmed against the payload, read again from
+// the decoded position of the string's first byte, which this mode keeps.
+//
 // The expected side is a template parameter of the scan (EX: slen / sbyte / auds
 // and the window's edges).  Expect is one; ProfileRef, one profile of a
 // Profiles table picked per token, is the other: claims_decide_each,
@@ -64,6 +72,7 @@
 #include <type_traits>
 
 #include "../../../include/jg.h"
+#include "claim_set.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define JG_CL_HD __host__ __device__ __forceinline__
@@ -388,6 +397,28 @@ static_assert(sizeof(ArgPreds) == 128 + 4 + 7 * 16 + 4 + 3 * 16 + 32 + 1024 && s
 static_assert(JG_MAX_ARGS == 4 && JG_PRED_VALUE_MAX <= 255, "four operand lengths in one dword");
 static_assert(JG_MAX_HASH_ARGS <= JG_MAX_ARGS, "a hashed column is a string column of the kernel");
 
+// The set side of jg_claims_match_set's predicates, behind ArgPreds in LDS: per
+// path the predicates a string arms (IN_SET) and those a string element of the
+// path's array arms (ELEMENT_IN_SET), per predicate the set of the call it asks,
+// and the call's sets as a lookup reads them.  The two pointers are device
+// addresses kept as integers: they are read back from LDS and used as they are.
+struct SetHeader {
+  uint64_t slots, pool;                               // jgset::Slot[mask + 1], the pool's dwords
+  uint32_t mask, maxprobe, seed, n;                   // n is not read by the scan: it keeps the header 32 bytes and self-describing
+};
+struct SetPreds {
+  uint16_t inset[JG_MAX_PATHS];
+  uint16_t elemset[JG_MAX_PATHS];
+  uint8_t set[JG_MAX_PRED];                           // the set index of a set predicate
+  uint32_t nsets, pad_;
+  SetHeader h[JG_MAX_SETS];
+};
+struct SetArgPreds : ArgPreds {
+  SetPreds sets;
+};
+static_assert(sizeof(SetHeader) == 32 && sizeof(SetPreds) == 16 + 16 + 16 + 8 + 32 * JG_MAX_SETS, "no padding in the set side");
+static_assert(sizeof(SetArgPreds) == sizeof(ArgPreds) + sizeof(SetPreds), "the set side lies right behind the predicates");
+
 // Fills *Q from the ABI's jg_preds as jg_claims_match_args reads it, for the
 // resolved paths P and the column counts of the same call.  Ops 1..4 are held to
 // resolve_preds' rules.  False also for: a column count over JG_MAX_ARGS, an
@@ -400,9 +431,18 @@ static_assert(JG_MAX_HASH_ARGS <= JG_MAX_ARGS, "a hashed column is a string colu
 // JG_PRED_IS_STRING (no value).  False also for: nhash over JG_MAX_HASH_ARGS,
 // nstr + nhash over JG_MAX_ARGS, two EQUALS_HASH of one path and column, two
 // IS_STRING of one path.
+// With SP (jg_claims_match_set) the list may also hold JG_PRED_IN_SET and
+// JG_PRED_ELEMENT_IN_SET -- one value byte, the set index < nsets -- whose masks
+// and indices go to *SP (its headers are the caller's to fill).  False also for:
+// nsets over JG_MAX_SETS, two of them of one path, op and set.
 inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, uint32_t nnum, ArgPreds* Q,
-                              bool hash_ops = false, uint32_t nhash = 0) {
+                              bool hash_ops = false, uint32_t nhash = 0, uint32_t nsets = 0, SetPreds* SP = nullptr) {
   if (x.n > JG_MAX_PRED || nstr > JG_MAX_ARGS || nnum > JG_MAX_ARGS) return false;
+  if (nsets > JG_MAX_SETS || (nsets && !SP)) return false;
+  if (SP) {
+    *SP = SetPreds{};
+    SP->nsets = nsets;
+  }
   if (nhash > JG_MAX_HASH_ARGS || nstr + nhash > JG_MAX_ARGS || (nhash && !hash_ops)) return false;
   *Q = ArgPreds{};
   uint8_t path[JG_MAX_PRED] = {}, rawop[JG_MAX_PRED] = {};
@@ -410,13 +450,15 @@ inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, 
   uint32_t o = 0, po = 0;                                         // within x.values, within the pool
   for (uint32_t k = 0; k < x.n; ++k) {
     const uint32_t p = x.path[k], op = x.op[k], l = x.value_len[k];
-    if (p >= P.n || op < JG_PRED_EQUALS || op > (hash_ops ? (uint32_t)JG_PRED_IS_STRING : (uint32_t)JG_PRED_NUM_LE_ARG))
+    if (p >= P.n || op < JG_PRED_EQUALS ||
+        op > (SP ? (uint32_t)JG_PRED_ELEMENT_IN_SET : hash_ops ? (uint32_t)JG_PRED_IS_STRING : (uint32_t)JG_PRED_NUM_LE_ARG))
       return false;
+    const bool setop = op >= JG_PRED_IN_SET;
     const bool konst = op <= JG_PRED_PRESENT;
     const bool hash = op == JG_PRED_EQUALS_HASH, isstr = op == JG_PRED_IS_STRING;
     const bool arg = op == JG_PRED_EQUALS_ARG || op == JG_PRED_NUM_GE_ARG || op == JG_PRED_NUM_LE_ARG || hash;
     const bool num = op >= JG_PRED_NUM_GE && op <= JG_PRED_NUM_LE_ARG;
-    const uint32_t lo = konst ? (op == JG_PRED_EQUALS || op == JG_PRED_PRESENT ? 0u : 1u) : arg ? 1u : isstr ? 0u : 8u;
+    const uint32_t lo = konst ? (op == JG_PRED_EQUALS || op == JG_PRED_PRESENT ? 0u : 1u) : arg || setop ? 1u : isstr ? 0u : 8u;
     const uint32_t hi = konst ? (op == JG_PRED_PRESENT ? 0u : (uint32_t)JG_PRED_VALUE_MAX) : lo;
     if (l < lo || l > hi || (l && !x.values)) return false;
     if (konst) {
@@ -431,6 +473,9 @@ inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, 
     } else if (arg) {
       if (x.values[o] >= (hash ? nhash : op == JG_PRED_EQUALS_ARG ? nstr : nnum)) return false;
       Q->col[k] = (uint8_t)(x.values[o] + (hash ? nstr : 0u));
+    } else if (setop) {
+      if (x.values[o] >= nsets) return false;
+      SP->set[k] = x.values[o];
     } else if (!isstr) {
       uint64_t b8 = 0;
       for (uint32_t b = 0; b < 8u; ++b) b8 |= (uint64_t)x.values[o + b] << (8u * b);
@@ -455,6 +500,8 @@ inline bool resolve_arg_preds(const jg_preds& x, const Paths& P, uint32_t nstr, 
     if (op == JG_PRED_HAS_ELEMENT) Q->elem[p] |= bit;
     if (num) Q->num[p] |= bit;
     if (isstr) Q->isstr[p] |= bit;
+    if (op == JG_PRED_IN_SET) SP->inset[p] |= bit;
+    if (op == JG_PRED_ELEMENT_IN_SET) SP->elemset[p] |= bit;
     if (arg) Q->arg |= bit;
     if (op == JG_PRED_NUM_LE || op == JG_PRED_NUM_LE_ARG) Q->le |= bit;
     o += l;
@@ -570,22 +617,35 @@ struct MatchArgsState : MatchState {
   uint32_t win[JG_MAX_ARGS] = {};   // per column: bytes [pos & ~3, (pos & ~3) + 4) of the lane's operand
 };
 
+// What the matching form with sets (claims_match_set) keeps beside
+// MatchArgsState's: the decoded position of the byte being read (as Extract's),
+// the set predicates the open string has armed, where that string's first byte
+// lies, and its running hash: one for every set of the call.
+struct MatchSetState : MatchArgsState {
+  uint32_t dpos = 0;
+  uint32_t sarm = 0;                // the IN_SET / ELEMENT_IN_SET predicates of the open string
+  uint32_t sstart = 0;              // the decoded position of its first byte
+  uint32_t sh = 0;                  // the hash state of the string so far (claim_set.hpp set_hash_step)
+};
+
 // The scan's compile-time modes: the verdict alone, with the jg_claims record,
 // with the record and the caller's selected members (jg_selected) by name or by
 // path, with the caller's predicates on members reached by path, and with
-// predicates that also take an operand per token or test a number
-constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3, kMatch = 4, kMatchArgs = 5;
+// predicates that also take an operand per token or test a number, and with
+// predicates that also ask a resident set
+constexpr int kVerdict = 0, kExtract = 1, kSelect = 2, kPath = 3, kMatch = 4, kMatchArgs = 5, kMatchSet = 6;
 // what a mode keeps: the jg_claims record, the jg_selected record, the path matcher, the predicates
 template <int M> constexpr bool kRec = M >= kExtract && M <= kPath;
 template <int M> constexpr bool kSel = M >= kSelect && M <= kPath;
-template <int M> constexpr bool kWalk = M == kPath || M == kMatch || M == kMatchArgs;
-template <int M> constexpr bool kPred = M == kMatch || M == kMatchArgs;
+template <int M> constexpr bool kWalk = M == kPath || M == kMatch || M == kMatchArgs || M == kMatchSet;
+template <int M> constexpr bool kPred = M == kMatch || M == kMatchArgs || M == kMatchSet;
+template <int M> constexpr bool kArgs = M == kMatchArgs || M == kMatchSet;      // operands of the token's own, numeric tests
 
 template <int M>
-struct ScanT : std::conditional_t<M == kMatchArgs, MatchArgsState,
+struct ScanT : std::conditional_t<M == kMatchSet, MatchSetState, std::conditional_t<M == kMatchArgs, MatchArgsState,
                                   std::conditional_t<M == kMatch, MatchState, std::conditional_t<M == kPath, ExtractPath,
                                   std::conditional_t<M == kSelect, ExtractSelect,
-                                  std::conditional_t<M == kExtract, Extract, NoExtract>>>>> {
+                                  std::conditional_t<M == kExtract, Extract, NoExtract>>>>>> {
   uint32_t st = ST_START;
   uint32_t depth = 0, stk = 0;      // open containers; bit d: container d+1 is an object
   uint32_t field = F_NONE;          // the top-level member whose value comes next
@@ -739,9 +799,17 @@ JG_CL_HD void begin_value(ScanT<M>& s, uint32_t c, const EX& E, const PQ* Q = nu
     s.mcand = !str ? 0u : slot ? Q->str[slot - 1u] : el ? Q->elem[el - 1u] : 0u;
     s.mword = str && slot ? Q->word[slot - 1u] : 0u;
     s.wpos = 0;
-    if constexpr (M == kMatchArgs) {
+    if constexpr (kArgs<M>) {
       s.nump = slot ? Q->num[slot - 1u] : 0u;          // read by end_number, if this is one
       s.res |= str && slot ? Q->isstr[slot - 1u] : 0u; // IS_STRING holds from the opening quote; "" counts
+    }
+    if constexpr (M == kMatchSet) {
+      // the set predicates arm where mcand does; the string's hash starts over
+      s.sarm = !str ? 0u : slot ? Q->sets.inset[slot - 1u] : el ? Q->sets.elemset[el - 1u] : 0u;
+      if (s.sarm) {
+        s.sstart = s.dpos + 1u;
+        s.sh = jgset::kHashBasis;
+      }
     }
     if (c == '[' && slot) {
       s.marr = slot;
@@ -819,7 +887,7 @@ JG_CL_HD void end_number(ScanT<M>& s, const PQ* Q = nullptr, const AR* A = nullp
     s.iat = s.field == F_IAT ? v : s.iat;
     if constexpr (kRec<M>) s.present |= 1u << s.field;
   }
-  if constexpr (M == kMatchArgs) {
+  if constexpr (kArgs<M>) {
     // The number a path with numeric predicates reaches.  Go holds it as a float64 f and the caller
     // tests f >= float64(B) or f <= float64(B).  On the date form -?(0|[1-9][0-9]{0,14}) (-0 is 0, as
     // in float64) the integer compare below is that compare for every int64 B: |v| < 10^15 < 2^53, so f
@@ -844,6 +912,17 @@ JG_CL_HD void end_number(ScanT<M>& s, const PQ* Q = nullptr, const AR* A = nullp
   // this byte may go on to close the object around the number, itself selected by a shorter path
   if constexpr (M == kPath) sel_commit(s);
   s.st = ST_AFTER;
+}
+
+// base64url alphabet -> 6 bits, 0xff for any other byte
+JG_CL_HD uint32_t sextet(uint32_t c) {
+  uint32_t v = 0xffu;
+  v = c - 0x41u < 26u ? c - 0x41u : v;
+  v = c - 0x61u < 26u ? c - 0x61u + 26u : v;
+  v = c - 0x30u < 10u ? c - 0x30u + 52u : v;
+  v = c == 0x2du ? 62u : v;
+  v = c == 0x5fu ? 63u : v;
+  return v;
 }
 
 template <int M, class EX, class SL, class PQ = Preds, class AR = NoArgs>
@@ -939,11 +1018,42 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const PQ* 
               const uint32_t k = (uint32_t)__builtin_ctz(mm);
               mm &= mm - 1u;
               uint32_t l = Q->len[k];
-              if constexpr (M == kMatchArgs) l = (Q->arg >> k) & 1u ? (s.alen >> (8u * Q->col[k])) & 0xffu : l;
+              if constexpr (kArgs<M>) l = (Q->arg >> k) & 1u ? (s.alen >> (8u * Q->col[k])) & 0xffu : l;
               s.res |= l == ((s.mword >> k) & 1u ? s.wpos : s.pos) ? 1u << k : 0u;
             }
             s.mcand = 0;
             s.mword = 0;
+          }
+          if constexpr (M == kMatchSet) {
+            // The armed set predicates: the string's hash, finalised with the seed of the predicate's set, is looked up in
+            // that set's table, and a slot of this hash and length is confirmed against the string
+            // itself, decoded again from the payload: byte o is byte o % 3 of group o / 3, a group
+            // the scan has read already (sextets valid, inside the segment's seven bytes of slack).
+            uint32_t mm = s.sarm;
+            if (mm) {
+              uint32_t cg = 0xffffffffu, trip = 0;
+              const uint32_t start = s.sstart;
+              auto cmp = [&](uint32_t i) -> uint32_t {
+                const uint32_t o = start + i, g = o / 3u;
+                if (g != cg) {
+                  const uint32_t w = A->peek(g);
+                  cg = g;
+                  trip = ((sextet(w & 0xffu) & 63u) << 18) | ((sextet((w >> 8) & 0xffu) & 63u) << 12) |
+                         ((sextet((w >> 16) & 0xffu) & 63u) << 6) | (sextet(w >> 24) & 63u);
+                }
+                return (trip >> (16u - 8u * (o - 3u * g))) & 0xffu;
+              };
+              while (mm) {
+                const uint32_t k = (uint32_t)__builtin_ctz(mm);
+                mm &= mm - 1u;
+                const uint32_t x = Q->sets.set[k];
+                const SetHeader& H = Q->sets.h[x];
+                const jgset::View V{(const jgset::Slot*)(uintptr_t)H.slots, (const uint32_t*)(uintptr_t)H.pool,
+                                    H.mask, H.maxprobe, H.seed, H.n};
+                s.res |= jgset::set_probe(V, jgset::set_hash_final(s.sh, H.seed), s.pos, cmp) ? 1u << k : 0u;
+              }
+              s.sarm = 0;
+            }
           }
           end_value(s);
         }
@@ -980,7 +1090,7 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const PQ* 
           while (mm) {
             const uint32_t k = (uint32_t)__builtin_ctz(mm);
             mm &= mm - 1u;
-            if constexpr (M == kMatchArgs) {
+            if constexpr (kArgs<M>) {
               // An operand of the lane's own: its length from alen, its byte from the column's window,
               // which is filled from global memory at every fourth byte while the candidate survives.
               if ((Q->arg >> k) & 1u) {
@@ -1002,6 +1112,9 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const PQ* 
           }
           s.mcand |= sp;
           s.wpos = sp ? 0u : s.wpos + 1u;
+        }
+        if constexpr (M == kMatchSet) {
+          s.sh = s.sarm ? jgset::set_hash_step(s.sh, c) : s.sh;
         }
         uint32_t m = s.cand;
         while (m) {
@@ -1073,17 +1186,6 @@ JG_CL_HD void step(ScanT<M>& s, uint32_t c, const EX& E, const SL* S, const PQ* 
   }
 }
 
-// base64url alphabet -> 6 bits, 0xff for any other byte
-JG_CL_HD uint32_t sextet(uint32_t c) {
-  uint32_t v = 0xffu;
-  v = c - 0x41u < 26u ? c - 0x41u : v;
-  v = c - 0x61u < 26u ? c - 0x61u + 26u : v;
-  v = c - 0x30u < 10u ? c - 0x30u + 52u : v;
-  v = c == 0x2du ? 62u : v;
-  v = c == 0x5fu ? 63u : v;
-  return v;
-}
-
 // jwt/jwt.go:117-199 on the scanned fields, in Validate's order
 template <int M, class EX>
 JG_CL_HD uint8_t verdict(const ScanT<M>& s, const EX& E) {
@@ -1116,7 +1218,7 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
   if constexpr (kSel<M>) *sel = jg_selected{};
   if ((len & 3u) == 1u) return JG_CL_HOST;
   ScanT<M> s;
-  if constexpr (M == kMatchArgs) {
+  if constexpr (kArgs<M>) {
     for (uint32_t x = 0; x < JG_MAX_ARGS; ++x) s.alen |= x < A->nstr() ? A->slen(x) << (8u * x) : 0u;
   }
   const uint32_t groups = (len + 3u) >> 2;
@@ -1131,7 +1233,7 @@ JG_CL_HD uint8_t scan_segment(Src& src, uint32_t len, const EX& E, jg_claims* ou
     // Go's strict decoding: the bits the last group does not use are zero
     if (nb < 3u && (trip & (nb == 1u ? 0xffffu : 0xffu))) return JG_CL_HOST;
     for (uint32_t k = 0; k < nb; ++k) {
-      if constexpr (kRec<M>) s.dpos = 3u * g + k;
+      if constexpr (kRec<M> || M == kMatchSet) s.dpos = 3u * g + k;
       step(s, (trip >> 16) & 0xffu, E, S, Q, A);
       if constexpr (kSel<M>) sel_commit(s);
       trip <<= 8;
@@ -1248,6 +1350,18 @@ JG_CL_HD uint8_t claims_match_args(Src& src, uint32_t len, const Profiles& T, ui
   return scan_segment<kMatchArgs>(src, len, E, nullptr, &P, nullptr, &Q, match, &A);
 }
 
+// claims_match_args' code and mask for a list of its ops, always (IS_STRING
+// included), and the two ops of jg_claims_match_set (include/jg.h): A is
+// claims_match_args' and also gives the segment again --
+//   uint32_t peek(uint32_t g)              Src::word(g), for any group the scan has read, in any order
+// No code changes and none becomes JG_CL_HOST because of the two ops.
+template <class Src, class AR>
+JG_CL_HD uint8_t claims_match_set(Src& src, uint32_t len, const Profiles& T, uint32_t p, const Paths& P,
+                                  const SetArgPreds& Q, const AR& A, uint32_t* match) {
+  const ProfileRef E{T, p};
+  return scan_segment<kMatchSet>(src, len, E, nullptr, &P, nullptr, &Q, match, &A);
+}
+
 }  // namespace jgclaims
 
 #if defined(__HIPCC__)
@@ -1263,6 +1377,8 @@ JG_CL_HD uint8_t claims_match_args(Src& src, uint32_t len, const Profiles& T, ui
 //   paths, apreds, match_out  k_claims_match_args: the same with apreds in the place of preds, and job i's operands:
 //                             arg_str[i * nstr + c] (a span of arg_bytes, which has ARENA_SLACK behind it) and
 //                             arg_num[i * nnum + c]
+//   paths, spreds, match_out  k_claims_match_set: the same with spreds in the place of apreds (its set headers hold
+//                             device addresses); picked only for a list that names a set op
 struct ClaimsLaunch {
   const uint8_t* arena = nullptr;
   const jg_cjob* jobs = nullptr;
@@ -1273,6 +1389,7 @@ struct ClaimsLaunch {
   const jgclaims::Paths* paths = nullptr;
   const jgclaims::Preds* preds = nullptr;
   const jgclaims::ArgPreds* apreds = nullptr;
+  const jgclaims::SetArgPreds* spreds = nullptr;
   const uint8_t* arg_bytes = nullptr;
   const jg_sarg* arg_str = nullptr;
   const int64_t* arg_num = nullptr;

@@ -296,6 +296,71 @@ def IsString(path_or_name) -> ArgRequire:
     return ArgRequire(path_or_name, ArgRequire.IS_STRING)
 
 
+class ClaimSet:
+    """A set of strings a claim can be held against: a deny-list of revoked jti, the
+    tenants a gateway serves.  Made by Validator.NewClaimSet; it owns one of the 16
+    set ids of the validator's key set until Close() (or until it is collected).
+    A set all of whose members the device takes -- at most 255 bytes, each printable
+    ASCII without quote and backslash -- is resident on the device and asked by the
+    scan; any other set is host-only (info()["host_only"]) and every token of a
+    call that names it is answered from the host path: no result depends on it."""
+
+    def __init__(self, validator, members, seed=None):
+        self._validator = validator                      # the context the set lives in
+        self._impl = validator._impl.new_claim_set(_members_of(members), seed)
+
+    def Replace(self, members, seed=None):
+        """The whole set anew, under the same id.  A failure (a NUL in a member:
+        ValueError; no room on the device: RuntimeError) leaves the old members in force."""
+        self._impl.replace(_members_of(members), seed)
+
+    def Close(self):
+        """Frees the id now; a later call that names the set raises ValueError."""
+        self._impl.close()
+
+    def info(self) -> dict:
+        """n, host_only and, of the resident table, nslots, maxprobe, seed, pool_bytes, generation"""
+        return dict(self._impl.info())
+
+    def __len__(self):
+        return len(self._impl)
+
+
+def _members_of(members):
+    out = []
+    for m in members:
+        if isinstance(m, (bytes, bytearray)):
+            m = bytes(m).decode("utf-8", "surrogateescape")
+        elif not isinstance(m, str):
+            raise TypeError("ClaimSet: a member is a str")
+        out.append(m)
+    return out
+
+
+class SetRequire(tuple):
+    """A requirement whose other side is a ClaimSet: (path, op, claim set).  Built by InSet and AnyElementIn."""
+    IN_SET, ELEMENT_IN_SET = 12, 13                      # jg_pred_op (include/jg.h)
+
+    def __new__(cls, path_or_name, op, claim_set):
+        path = path_or_name if isinstance(path_or_name, Path) else Path(path_or_name)
+        if not isinstance(claim_set, ClaimSet):
+            raise TypeError("SetRequire: the set is a ClaimSet (Validator.NewClaimSet)")
+        return super().__new__(cls, (path, int(op), claim_set))
+
+    def __repr__(self):
+        return "%s(%r, <ClaimSet of %d>)" % ("InSet" if self[1] == self.IN_SET else "AnyElementIn", self[0], len(self[2]))
+
+
+def InSet(path_or_name, claim_set: ClaimSet) -> SetRequire:
+    """The claim is a string equal to a member of the set."""
+    return SetRequire(path_or_name, SetRequire.IN_SET, claim_set)
+
+
+def AnyElementIn(path_or_name, claim_set: ClaimSet) -> SetRequire:
+    """The claim is an array and one of its direct elements is a string equal to a member of the set."""
+    return SetRequire(path_or_name, SetRequire.ELEMENT_IN_SET, claim_set)
+
+
 def _arg_requires_of(requires):
     out = []
     for r in requires:
@@ -303,9 +368,11 @@ def _arg_requires_of(requires):
             out.append((list(r[0]), r[1], r[2], 0, 0))
         elif isinstance(r, ArgRequire):
             out.append((list(r[0]), r[1], r[2], r[3], r[4]))
+        elif isinstance(r, SetRequire):
+            out.append((list(r[0]), r[1], "", 0, r[2]._impl.token()))    # the handle travels as its token
         else:
             raise TypeError("requires: elements are built by Equals, HasWord, HasElement, Present, EqualsEach, "
-                            "AtLeast, AtMost, AtLeastEach, AtMostEach, HashOfEach or IsString")
+                            "AtLeast, AtMost, AtLeastEach, AtMostEach, HashOfEach, IsString, InSet or AnyElementIn")
     return out
 
 
@@ -333,6 +400,13 @@ class Validator:
 
     def Validate(self, token, expected: Expected = None, ctx=None):
         return tuple(self._impl.validate(token, (expected or Expected())._native()))
+
+    def NewClaimSet(self, members, seed: int = None) -> "ClaimSet":
+        """A ClaimSet of `members` (str) on this validator's key set, for InSet and
+        AnyElementIn in the MatchBatchArgs family.  A NUL in a member: ValueError; a
+        17th live set, or no room on the device: RuntimeError.  `seed` fixes the
+        table's seed (tests); it is random per load otherwise."""
+        return ClaimSet(self, members, seed)
 
     def ValidateBatch(self, tokens: Sequence, expected: Expected = None, ctx=None):
         """BASELINE north star: per-token result == Validate(tokens[i], expected)."""
@@ -638,5 +712,5 @@ def NewValidator(keyset: Optional[KeySet]):
 __all__ = ["RS256", "RS384", "RS512", "ES256", "ES384", "ES512", "PS256", "PS384", "PS512", "EdDSA",
            "DefaultLeewaySeconds", "PublicKey", "SupportedSigningAlgorithm", "ParsePublicKeyPEM", "KeySet",
            "NewStaticKeySet", "NewJSONWebKeySet", "NewOIDCDiscoveryKeySet", "Expected", "Path", "Validator",
-           "NewValidator", "Require", "Equals", "HasWord", "HasElement", "Present", "ArgRequire", "EqualsEach",
+           "NewValidator", "ClaimSet", "SetRequire", "InSet", "AnyElementIn", "Require", "Equals", "HasWord", "HasElement", "Present", "ArgRequire", "EqualsEach",
            "AtLeast", "AtMost", "AtLeastEach", "AtMostEach", "HashOfEach", "IsString"]

@@ -735,6 +735,80 @@ int jg_claims_match_hash(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
                          const jg_hargs* hargs /* may be NULL: nhash 0 */,
                          uint8_t* code_out, uint32_t* match_out);
 
+/* Resident sets and set-membership predicates: "is this claim one of many?" -- a
+ * jti on a deny-list of revoked ids, an iss / azp / tid among the tenants a
+ * gateway serves -- answered in the scan's own pass, against a hash table that
+ * stays on the device between calls.
+ *
+ * jg_set_load builds the set `id` (0..JG_MAX_LOADED_SETS - 1) of the context from
+ * n members, member k being bytes[off, off + len) of members[k], and uploads it.
+ * A member is 0..JG_SET_MEMBER_MAX bytes, each in 0x20..0x7e and neither a quote
+ * nor a backslash (a predicate value's rule); "" is a legal member, a repeated
+ * member is folded into its first occurrence, an empty set is legal and matches
+ * nothing; at most 2^24 distinct members and a pool under 2^32 bytes.  The table
+ * is built on the host, deterministically from the members in their order and
+ * `seed` (kernels/claim_set_build.hpp set_build), and uploaded on a stream of its own
+ * to the context's FIRST device -- where every claims scan runs; nothing is
+ * placed on the others.  The set is published whole: a scan captures the sets it
+ * names when it starts, so a load never waits for a scan and never changes one
+ * in flight, and a replaced set's memory is released when the last scan that
+ * captured it has ended.  Loading an id in use replaces it.  Any failure leaves
+ * the set that id named before in force: -1 (a refused member, named in
+ * jg_last_error; more than 2^24 distinct members, or lengths and bytes that come
+ * to 2^32 bytes of pool or more; id out of range; a needed pointer NULL), -2 (an allocation
+ * failure -- jg_debug_fail_alloc reaches these allocations too -- or a HIP error).
+ * jg_set_free drops the id (-1: out of range or not loaded); jg_set_info reports
+ * a loaded set (-1 likewise): `generation` counts the context's successful loads
+ * and is different for every one of them.  With CAPJWT_LOAD_TRACE=1 a load
+ * prints its host build and its upload time on stderr, as jg_keys_load does. */
+#define JG_MAX_SETS 4            /* sets one scan call may name */
+#define JG_MAX_LOADED_SETS 16    /* ids 0..15 per context */
+#define JG_SET_MEMBER_MAX 255
+typedef struct jg_setinfo {
+  uint32_t n, nslots, maxprobe, seed;        /* distinct members, table slots, longest probe run, the seed */
+  uint64_t pool_bytes, generation;
+} jg_setinfo;
+int jg_set_load(jg_ctx* ctx, uint32_t id, const uint8_t* bytes, size_t bytes_len,
+                const jg_sarg* members, size_t n, uint32_t seed);
+int jg_set_free(jg_ctx* ctx, uint32_t id);
+int jg_set_info(jg_ctx* ctx, uint32_t id, jg_setinfo* out);
+/* Testing aid: the table (nslots pairs hash, ref) and the pool (pool_bytes / 4
+ * dwords) of a loaded set, copied back from the device as they lie there, for a
+ * byte-for-byte compare with the host build.  -1: not loaded, an output NULL or
+ * a cap (in dwords pairs / dwords) below the set's size; -2: a HIP error. */
+int jg_debug_set_read(jg_ctx* ctx, uint32_t id, uint32_t* slots_out, size_t cap_slots, uint32_t* pool_out, size_t cap_pool);
+
+/* jg_claims_match_hash with two more ops, on sets loaded with jg_set_load; with
+ * v the value the walk reaches as for the other eleven:
+ *  - JG_PRED_IN_SET: v is a string whose bytes equal a member of set
+ *    sets->id[value byte];
+ *  - JG_PRED_ELEMENT_IN_SET: v is an array and one of its direct elements is a
+ *    string equal to a member of that set.  Other elements never match, nested
+ *    containers are not searched, and a string v does not match (HAS_ELEMENT's
+ *    rules).
+ * For both value_len is 1 and the value byte is an index below sets->nsets.  A
+ * string with a byte >= 0x80 is compared raw and so equals no member; one with
+ * an escape is JG_CL_HOST already.  A key named twice: the last member wins, as
+ * for every op.  Neither op changes a code and no payload is JG_CL_HOST because
+ * of them; the mask is 0 for HOST and bits n..31 are 0.  With no op >= 12 the
+ * outputs are jg_claims_match_hash's, byte for byte (and the kernel is the one
+ * that entry launches).  The scan hashes the string as it goes by and, at its
+ * closing quote, looks the hash up in the set's table; a slot whose hash and
+ * length agree is confirmed byte for byte against the payload, read again.
+ * -1: everything jg_claims_match_hash refuses (its unknown ops are here those
+ * outside 1..13); nsets over JG_MAX_SETS; an id of JG_MAX_LOADED_SETS or more,
+ * or not loaded; a set index that is not one byte below nsets; two predicates
+ * of the same path, op and set.  sets may be NULL: nsets 0. */
+enum { JG_PRED_IN_SET = 12, JG_PRED_ELEMENT_IN_SET = 13 };   /* jg_claims_match_set only */
+typedef struct jg_setargs { uint32_t nsets; uint32_t id[JG_MAX_SETS]; } jg_setargs;
+int jg_claims_match_set(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
+                        const jg_cjob* jobs, size_t njobs,
+                        const jg_expect* expects, uint32_t nexpect, const jg_paths* paths, const jg_preds* preds,
+                        const jg_args* args /* may be NULL: no plain columns */,
+                        const jg_hargs* hargs /* may be NULL: nhash 0 */,
+                        const jg_setargs* sets /* may be NULL: nsets 0 */,
+                        uint8_t* code_out, uint32_t* match_out);
+
 /* Library build information (gfx target, version). */
 const char* jg_version(void);
 
