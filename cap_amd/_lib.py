@@ -29,7 +29,7 @@ EXPORTS = ["jg_create", "jg_destroy", "jg_keys_load", "jg_verify_batch", "jg_las
            "jg_debug_max_upgrades", "jg_debug_lifetime_check", "jg_debug_fail_verify", "jg_debug_tables_built",
            "jg_debug_small_path", "jg_claims_scan", "jg_claims_extract", "jg_claims_select", "jg_claims_each",
            "jg_claims_paths", "jg_claims_match", "jg_claims_match_args", "jg_claims_match_hash",
-           "jg_set_load", "jg_set_free", "jg_set_info", "jg_debug_set_read", "jg_claims_match_set"]
+           "jg_set_load", "jg_set_free", "jg_set_info", "jg_debug_set_read", "jg_claims_match_set", "jg_set_add"]
 
 
 class JgKey(ctypes.Structure):
@@ -416,6 +416,7 @@ def lib():
                                           ctypes.POINTER(JgArgs), ctypes.POINTER(JgHArgs), ctypes.POINTER(JgSetArgs),
                                           vp, vp]
         L.jg_set_load.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz, ctypes.c_uint32]
+        L.jg_set_add.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_uint32)]
         L.jg_set_free.argtypes = [vp, ctypes.c_uint32]
         L.jg_set_info.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(JgSetInfo)]
         L.jg_debug_set_read.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, sz]
@@ -799,6 +800,27 @@ class Context:
                                len(spans), int(seed) & 0xffffffff)
         if rc != 0:
             raise JgError(f"jg_set_load rc={rc}: {self.error()}")
+
+    def set_add(self, set_id, members, spans=None, want_added=True):
+        """jg_set_add: adds `members` (a list of bytes) to the loaded set `set_id`
+        on the device -> how many were not in it (None with want_added=False, which
+        passes NULL).  `spans` as set_load takes it."""
+        members = [bytes(m) for m in members]
+        blob = b"".join(members)
+        if spans is None:
+            spans, o = [], 0
+            for m in members:
+                spans.append((o, len(m)))
+                o += len(m)
+        sp = (JgSArg * max(1, len(spans)))()
+        for t, (off, ln) in zip(sp, spans):
+            t.off, t.len = off, ln
+        added = ctypes.c_uint32(0xeeeeeeee)
+        rc = lib().jg_set_add(self.h, int(set_id), blob or b"\0", len(blob), ctypes.cast(sp, ctypes.c_void_p),
+                              len(spans), ctypes.byref(added) if want_added else None)
+        if rc != 0:
+            raise JgError(f"jg_set_add rc={rc}: {self.error()}")
+        return added.value if want_added else None
 
     def set_free(self, set_id):
         """jg_set_free"""

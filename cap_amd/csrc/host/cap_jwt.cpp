@@ -1912,7 +1912,45 @@ const char* claim_code_error(uint8_t code) {
 }  // namespace
 
 // ---- ClaimSet: what a handle shares ----
-using HostSet = std::unordered_set<std::string>;
+// The host copy: immutable parts, parts[0] the base and the rest what ClaimSet::Add
+// has added since, disjoint.  A snapshot (MatchPlan) shares the parts; an Add makes
+// a new HostSet of the same parts and one more, never a copy of the members: two
+// trailing parts of like size are merged (as a binary counter carries, so there
+// are O(log n) parts and an Add of k members costs O(k) amortised), and all are
+// folded into a new base once those added pass one eighth of it.
+struct HostSet {
+  using Part = std::unordered_set<std::string>;
+  std::vector<std::shared_ptr<const Part>> parts;
+  size_t n = 0;
+  size_t size() const { return n; }
+  size_t count(const std::string& m) const {
+    for (const auto& p : parts)
+      if (p->count(m)) return 1;
+    return 0;
+  }
+  static std::shared_ptr<const HostSet> of(Part&& base) {
+    auto h = std::make_shared<HostSet>();
+    h->n = base.size();
+    h->parts.push_back(std::make_shared<const Part>(std::move(base)));
+    return h;
+  }
+  // this set and `fresh`, none of which it holds
+  std::shared_ptr<const HostSet> with(Part&& fresh) const {
+    auto h = std::make_shared<HostSet>(*this);
+    h->n += fresh.size();
+    h->parts.push_back(std::make_shared<const Part>(std::move(fresh)));
+    const auto merge_last = [&h] {
+      Part u(*h->parts[h->parts.size() - 2]);
+      u.insert(h->parts.back()->begin(), h->parts.back()->end());
+      h->parts.pop_back();
+      h->parts.back() = std::make_shared<const Part>(std::move(u));
+    };
+    while (h->parts.size() > 2 && 2 * h->parts.back()->size() >= h->parts[h->parts.size() - 2]->size()) merge_last();
+    if (8 * (h->n - h->parts[0]->size()) > h->parts[0]->size())
+      while (h->parts.size() > 1) merge_last();
+    return h;
+  }
+};
 struct ClaimSetImpl {
   Engine* eng = nullptr;
   int id = -1;
@@ -3442,6 +3480,7 @@ __attribute__((weak)) int jg_claims_match_set(jg_ctx*, const uint8_t*, size_t, c
                                               uint32_t, const jg_paths*, const jg_preds*, const jg_args*, const jg_hargs*,
                                               const jg_setargs*, uint8_t*, uint32_t*);
 __attribute__((weak)) int jg_set_load(jg_ctx*, uint32_t, const uint8_t*, size_t, const jg_sarg*, size_t, uint32_t);
+__attribute__((weak)) int jg_set_add(jg_ctx*, uint32_t, const uint8_t*, size_t, const jg_sarg*, size_t, uint32_t*);
 __attribute__((weak)) int jg_set_free(jg_ctx*, uint32_t);
 __attribute__((weak)) int jg_set_info(jg_ctx*, uint32_t, jg_setinfo*);
 }
@@ -3498,6 +3537,35 @@ void Engine::set_store(int id, const std::vector<std::string>& members, uint32_t
   }
 }
 
+void Engine::set_add(int id, const std::vector<std::string>& members) {
+  if (members.empty()) return;
+  std::shared_lock<std::shared_mutex> life(life_);
+  std::lock_guard<std::mutex> g(set_mu_);
+  if (!ctx_) throw std::runtime_error("capjwt: claim set not added to: device lost: " + lost_);
+  SetRecord& r = sets_[id];
+  if (!r.live || !r.stored) throw std::runtime_error("capjwt: claim set not added to: the id holds no set");
+  const size_t nbytes = r.bytes.size(), nspans = r.spans.size();
+  for (const std::string& m : members) {
+    r.spans.emplace_back((uint32_t)r.bytes.size(), (uint32_t)m.size());
+    r.bytes += m;
+  }
+  int rc = 0;
+  const char* entry = "jg_set_add";
+  if (jg_set_add) {
+    std::vector<jg_sarg> m(members.size());
+    for (size_t k = 0; k < m.size(); ++k) m[k] = jg_sarg{r.spans[nspans + k].first, r.spans[nspans + k].second};
+    rc = jg_set_add(ctx_, (uint32_t)id, (const uint8_t*)r.bytes.data(), r.bytes.size(), m.data(), m.size(), nullptr);
+  } else {                                            // an older library: the union loaded whole, the same set
+    entry = "jg_set_load";
+    rc = set_load_locked(id);
+  }
+  if (rc != 0) {
+    r.bytes.resize(nbytes);                           // what the id held before stays in force, here as on the device
+    r.spans.resize(nspans);
+    throw std::runtime_error(std::string("capjwt: ") + entry + ": " + jg_last_error(ctx_));
+  }
+}
+
 void Engine::set_release(int id) {
   std::shared_lock<std::shared_mutex> life(life_);
   std::lock_guard<std::mutex> g(set_mu_);
@@ -3532,22 +3600,23 @@ uint32_t random_seed() {
   return (uint32_t)rd();
 }
 // the members as both paths take them: the host copy, the distinct ones in order, and whether the device takes all
-void split_members(const std::vector<std::string>& members, std::shared_ptr<HostSet>* host, std::vector<std::string>* distinct,
+void split_members(const std::vector<std::string>& members, std::shared_ptr<const HostSet>* host, std::vector<std::string>* distinct,
                    bool* host_only) {
-  *host = std::make_shared<HostSet>();
+  HostSet::Part all;
   *host_only = false;
   for (const std::string& m : members) {
     if (m.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim set member holds a NUL byte");
-    if (!(*host)->insert(m).second) continue;
+    if (!all.insert(m).second) continue;
     distinct->push_back(m);
     if (!set_member_ok(m)) *host_only = true;
   }
+  *host = HostSet::of(std::move(all));
 }
 }  // namespace
 
 void ClaimSet::Replace(const std::vector<std::string>& members, std::optional<uint32_t> seed) {
   if (!impl) throw std::invalid_argument("capjwt: an empty ClaimSet handle");
-  std::shared_ptr<HostSet> host;
+  std::shared_ptr<const HostSet> host;
   std::vector<std::string> distinct;
   bool host_only = false;
   split_members(members, &host, &distinct, &host_only);
@@ -3557,6 +3626,32 @@ void ClaimSet::Replace(const std::vector<std::string>& members, std::optional<ui
   impl->eng->set_store(impl->id, host_only ? std::vector<std::string>() : distinct, seed ? *seed : random_seed());
   impl->host = std::move(host);
   impl->host_only = host_only;
+}
+
+size_t ClaimSet::Add(const std::vector<std::string>& members) {
+  if (!impl) throw std::invalid_argument("capjwt: an empty ClaimSet handle");
+  for (const std::string& m : members)
+    if (m.find('\0') != std::string::npos) throw std::invalid_argument("capjwt: a claim set member holds a NUL byte");
+  std::lock_guard<std::mutex> g(impl->mu);
+  if (impl->closed) throw std::invalid_argument("capjwt: the claim set is closed");
+  // only what the set does not hold goes on: the device's pool does not grow from repeats
+  HostSet::Part fresh;
+  std::vector<std::string> order;
+  bool refused = false;
+  for (const std::string& m : members) {
+    if (impl->host->count(m) || !fresh.insert(m).second) continue;
+    order.push_back(m);
+    if (!set_member_ok(m)) refused = true;
+  }
+  if (order.empty()) return 0;
+  if (!impl->host_only) {
+    // a member the device refuses: host-only from here on, as Replace with the union -- the id kept with nothing in it
+    if (refused) impl->eng->set_store(impl->id, std::vector<std::string>(), random_seed());
+    else impl->eng->set_add(impl->id, order);
+    impl->host_only = refused;
+  }
+  impl->host = impl->host->with(std::move(fresh));
+  return order.size();
 }
 
 void ClaimSet::Close() {
@@ -3601,7 +3696,7 @@ ClaimSet ClaimSet::from_token(uint32_t token) {
 }
 
 ClaimSet Validator::NewClaimSet(const std::vector<std::string>& members, std::optional<uint32_t> seed) {
-  std::shared_ptr<HostSet> host;
+  std::shared_ptr<const HostSet> host;
   std::vector<std::string> distinct;
   bool host_only = false;
   split_members(members, &host, &distinct, &host_only);   // throws before an id is taken

@@ -243,6 +243,11 @@ class Engine {
   };
   int set_acquire();
   void set_store(int id, const std::vector<std::string>& members, uint32_t seed);
+  // set_add() adds `members` (device-legal, distinct, none of them in the set) to
+  // the stored set on the device (jg_set_add) and to what recover() loads again;
+  // with a library that lacks jg_set_add the union is loaded whole (jg_set_load).
+  // A failure throws runtime_error and leaves what the id held before.
+  void set_add(int id, const std::vector<std::string>& members);
   void set_release(int id);
   SetInfo set_info(int id);
   // Pinned host memory for one call's arena (jg_host_alloc), from a small pool
@@ -566,6 +571,16 @@ class ClaimSet {
   // a device allocation or load failure: runtime_error) leaves the old members in
   // force on both paths.  seed: random per load unless given (tests).
   void Replace(const std::vector<std::string>& members, std::optional<uint32_t> seed = std::nullopt);
+  // Adds members; returns how many were new.  Only those the set does not hold yet
+  // go to the device (jg_set_add: a kernel inserts them into a copy of the resident
+  // table, published whole, so a scan in flight keeps the set it captured), and the
+  // host copy grows by an overlay, not by a copy: a call costs what it adds, not
+  // what the set holds.  A NUL in a member throws invalid_argument before anything
+  // changes; any failure (runtime_error) leaves the old members in force on both
+  // paths.  A member the device refuses turns the set host-only, as Replace with
+  // the union would; Add on a host-only set touches the host copy alone.  Throws
+  // after Close().  MatchPlans made before see the set as it was.
+  size_t Add(const std::vector<std::string>& members);
   void Close();                     // frees the id now; a later call that names the set throws
   uint32_t token() const;           // a process-wide number of this handle, for bindings: from_token() finds it again
   static ClaimSet from_token(uint32_t token);

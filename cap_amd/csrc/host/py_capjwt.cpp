@@ -802,6 +802,10 @@ PYBIND11_MODULE(_capjwt_host, m) {
         py::gil_scoped_release rel;
         s.set.Replace(members, seed);
       }, py::arg("members"), py::arg("seed") = py::none())
+      .def("add", [](PyClaimSet& s, const std::vector<std::string>& members) {
+        py::gil_scoped_release rel;
+        return s.set.Add(members);
+      }, py::arg("members"))
       .def("close", [](PyClaimSet& s) { s.set.Close(); })
       .def("token", [](PyClaimSet& s) { return s.set.token(); })
       .def("__len__", [](PyClaimSet& s) { return s.set.size(); })

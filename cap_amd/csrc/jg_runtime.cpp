@@ -50,6 +50,7 @@
 #include "kernels/ecdsa.hpp"
 #include "kernels/ed25519.hpp"
 #include "kernels/claim_set_build.hpp"
+#include "kernels/claim_set_insert.hpp"
 #include "kernels/claims.hpp"
 #include "kernels/hash.hpp"
 #include "kernels/hash_operand.hpp"
@@ -3994,6 +3995,120 @@ int jg_set_load(jg_ctx* ctx, uint32_t id, const uint8_t* bytes, size_t bytes_len
     return 0;
   } catch (const std::exception& e) {
     ctx->set_err(std::string("jg_set_load: ") + e.what());
+    return -2;
+  }
+}
+
+// Copy-on-write: a new table and a new pool are made on the set stream from the
+// old ones and the new members (kernels/claim_set_insert.hip), and published as
+// a new immutable LoadedSet only after the stream has drained.  The old set is
+// never written: a scan that captured it goes on reading it.  Every failure
+// returns before the swap.
+int jg_set_add(jg_ctx* ctx, uint32_t id, const uint8_t* bytes, size_t bytes_len,
+               const jg_sarg* members, size_t n, uint32_t* added) {
+  if (!ctx) return -1;
+  if (id >= JG_MAX_LOADED_SETS || (n > 0 && !members) || (bytes_len > 0 && !bytes)) {
+    ctx->set_err("jg_set_add: an id of 16 or more, or members or bytes NULL");
+    return -1;
+  }
+  try {
+    std::lock_guard<std::mutex> g(ctx->set_load_mu);
+    const LoadedSetP old = ctx->set_at(id);
+    if (!old) {
+      ctx->set_err("jg_set_add: set " + std::to_string(id) + " is not loaded");
+      return -1;
+    }
+    if (n == 0) {
+      if (added) *added = 0;
+      return 0;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    // the pool delta: one entry per member given, as set_build packs it; repeats are not folded (the kernel finds them)
+    uint64_t dwords = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const jg_sarg& m = members[k];
+      bool ok = m.len <= JG_SET_MEMBER_MAX && m.off <= bytes_len && m.len <= bytes_len - m.off;
+      for (uint32_t b = 0; ok && b < m.len; ++b) ok = jgset::member_byte_ok(bytes[m.off + b]);
+      if (!ok) {
+        ctx->set_err("jg_set_add: member " + std::to_string(k) + " is past the bytes, over 255 bytes or holds a byte "
+                     "that is not printable ASCII without quote and backslash");
+        return -1;
+      }
+      dwords += 1u + (m.len + 3u) / 4u;
+    }
+    if ((uint64_t)old->n + n > (uint64_t(1) << 24) || old->pool_bytes + dwords * 4u >= (uint64_t(1) << 32)) {
+      ctx->set_err("jg_set_add: more than 2^24 members with the new ones, or a pool of 4 GiB or more");
+      return -1;
+    }
+    const uint32_t old_dwords = (uint32_t)(old->pool_bytes / 4);
+    std::vector<uint32_t> delta((size_t)dwords, 0u), refs(n);
+    uint32_t at = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const jg_sarg& m = members[k];
+      delta[at] = m.len;
+      for (uint32_t b = 0; b < m.len; ++b) delta[at + 1u + (b >> 2)] |= (uint32_t)bytes[m.off + b] << (8u * (b & 3u));
+      refs[k] = old_dwords + at + 1u;
+      at += 1u + (m.len + 3u) / 4u;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    Device* d = ctx->devs[0].get();
+    const bool grow = 2 * ((uint64_t)old->n + n) > old->nslots;
+    uint32_t nslots = old->nslots;
+    if (grow)
+      for (nslots = 1; nslots < 2 * ((uint64_t)old->n + n);) nslots *= 2;
+    auto S = std::make_shared<LoadedSet>();
+    const size_t sbytes = sizeof(jgset::Slot) * nslots, obytes = (size_t)old->pool_bytes, pbytes = obytes + 4 * delta.size();
+    S->slots = dev_alloc(d->id, sbytes, &ctx->fail_alloc);
+    S->pool = dev_alloc(d->id, pbytes + ARENA_SLACK, &ctx->fail_alloc);
+    // the launch's own: the three words, then the refs; gone when this call returns
+    DevBufP tmp = dev_alloc(d->id, 16 + 4 * n, &ctx->fail_alloc);
+    jgset::InsertWords* words = tmp->as<jgset::InsertWords>();
+    uint32_t* drefs = (uint32_t*)((uint8_t*)tmp->p + 16);
+    HIPCHK(hipSetDevice(d->id));
+    const hipStream_t s = d->setstream;
+    jgset::InsertWords w{0u, grow ? 0u : old->maxprobe, 0u};
+    HIPCHK(hipMemcpyAsync(words, &w, sizeof w, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(drefs, refs.data(), 4 * n, hipMemcpyHostToDevice, s));
+    if (grow) {
+      HIPCHK(hipMemsetAsync(S->slots->p, 0, sbytes, s));
+      HIPCHK(jgset::launch_set_rehash(old->slots->as<jgset::Slot>(), old->nslots, S->slots->as<jgset::Slot>(), nslots, words, s));
+    } else {
+      HIPCHK(hipMemcpyAsync(S->slots->p, old->slots->p, sbytes, hipMemcpyDeviceToDevice, s));
+    }
+    if (obytes) HIPCHK(hipMemcpyAsync(S->pool->p, old->pool->p, obytes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync((uint8_t*)S->pool->p + obytes, delta.data(), 4 * delta.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync((uint8_t*)S->pool->p + pbytes, 0, ARENA_SLACK, s));
+    HIPCHK(jgset::launch_set_insert(S->slots->as<jgset::Slot>(), nslots, S->pool->as<uint32_t>(), drefs, (uint32_t)n, old->seed, words, s));
+    HIPCHK(hipMemcpyAsync(&w, words, sizeof w, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (w.error) {
+      ctx->set_err("jg_set_add: an insertion found no slot (error word " + std::to_string(w.error) + ")");
+      return -2;
+    }
+    S->n = old->n + w.added;
+    S->nslots = nslots;
+    S->maxprobe = w.maxprobe;
+    S->seed = old->seed;
+    S->pool_bytes = pbytes;
+    {
+      // jg_set_free does not take set_load_mu: an id freed since this call looked is not brought back
+      std::lock_guard<std::mutex> gs(ctx->set_mu);
+      if (ctx->sets[id] != old) {
+        ctx->set_err("jg_set_add: set " + std::to_string(id) + " was freed during the add");
+        return -1;
+      }
+      S->generation = ++ctx->set_generation;
+      ctx->sets[id] = std::move(S);
+    }
+    if (added) *added = w.added;
+    if (load_trace()) {                                 // CAPJWT_LOAD_TRACE=1, as jg_set_load's phases
+      const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+      std::fprintf(stderr, "[capjwt] jg_set_add id %u: %zu given, %u added, %u slots%s, pack %.1f ms, alloc + copy + kernels %.1f ms\n",
+                   id, n, w.added, nslots, grow ? " (rehashed)" : "", ms(t0, t1), ms(t1, std::chrono::steady_clock::now()));
+    }
+    return 0;                                           // `old` dies here, outside set_mu, unless a scan holds it
+  } catch (const std::exception& e) {
+    ctx->set_err(std::string("jg_set_add: ") + e.what());
     return -2;
   }
 }

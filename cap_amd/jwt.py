@@ -314,6 +314,13 @@ class ClaimSet:
         ValueError; no room on the device: RuntimeError) leaves the old members in force."""
         self._impl.replace(_members_of(members), seed)
 
+    def Add(self, members) -> int:
+        """Adds members -> how many were new.  Only those go to the device, where a
+        kernel inserts them (no rebuild, no upload of the whole set).  A failure (a NUL
+        in a member: ValueError; no room on the device: RuntimeError) leaves the old
+        members in force; a member the device does not take turns the set host-only."""
+        return self._impl.add(_members_of(members))
+
     def Close(self):
         """Frees the id now; a later call that names the set raises ValueError."""
         self._impl.close()

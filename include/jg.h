@@ -766,12 +766,42 @@ int jg_claims_match_hash(jg_ctx* ctx, const uint8_t* arena, size_t arena_len,
 #define JG_SET_MEMBER_MAX 255
 typedef struct jg_setinfo {
   uint32_t n, nslots, maxprobe, seed;        /* distinct members, table slots, longest probe run, the seed */
+                                             /* nslots: a power of two >= 2n; the smallest after a load, not always after jg_set_add */
   uint64_t pool_bytes, generation;
 } jg_setinfo;
 int jg_set_load(jg_ctx* ctx, uint32_t id, const uint8_t* bytes, size_t bytes_len,
                 const jg_sarg* members, size_t n, uint32_t seed);
 int jg_set_free(jg_ctx* ctx, uint32_t id);
 int jg_set_info(jg_ctx* ctx, uint32_t id, jg_setinfo* out);
+/* jg_set_add adds n members to the loaded set `id` on the device (DESIGN.md
+ * 10.10): a deny-list grows by a few ids without the host rebuilding and
+ * uploading it whole.  Members are given and checked as jg_set_load's; one that
+ * is refused is named in jg_last_error and nothing is added.  The call is
+ * copy-on-write, so all that holds of a load holds of it: it builds a new table
+ * and a new pool on the set stream of the first device -- the old table copied
+ * device to device, or rehashed by a kernel into the smallest power of two of at
+ * least 2 * (members before + n) slots when 2 * (members before + n) exceeds
+ * the old slot count; the old pool copied and the new entries uploaded behind
+ * it; the new entries placed by a kernel -- and publishes the result whole after
+ * the stream has drained, under the old seed and a new generation.  A scan in
+ * flight keeps the set it captured, an add never waits for a scan, and the old
+ * memory is released when its last holder has ended.  *added (may be NULL) is
+ * the number of members that were not in the set; a member already resident, or
+ * given twice, takes no slot, but its entry stays behind in the pool unused:
+ * pool_bytes grows by every entry handed in, and jg_set_load of the members
+ * compacts it.  After adds the slot count is a power of two of at least 2 * n
+ * and no longer necessarily the smallest; where among its probe run a member
+ * lies depends on the order in which the device's lanes arrived, so the table is
+ * not a function of the members alone (lookups do not depend on it).
+ * n == 0 returns 0 and publishes nothing: the generation is unchanged.  -1: id
+ * out of range or not loaded, a needed pointer NULL, a refused member, members
+ * before + n over 2^24, or a pool of 2^32 bytes or more.  -2: an allocation
+ * failure (jg_debug_fail_alloc reaches both allocations), a HIP error, or an
+ * insertion that found no slot.  Every failure leaves the id naming what it
+ * named, with the same generation.  CAPJWT_LOAD_TRACE=1 prints an add's phases
+ * as a load's. */
+int jg_set_add(jg_ctx* ctx, uint32_t id, const uint8_t* bytes, size_t bytes_len,
+               const jg_sarg* members, size_t n, uint32_t* added /* may be NULL */);
 /* Testing aid: the table (nslots pairs hash, ref) and the pool (pool_bytes / 4
  * dwords) of a loaded set, copied back from the device as they lie there, for a
  * byte-for-byte compare with the host build.  -1: not loaded, an output NULL or
