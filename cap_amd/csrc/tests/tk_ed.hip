@@ -1,11 +1,15 @@
 // tk_ed.hip -- TEST INFRASTRUCTURE (libcapjwt_tk.so only, never the product
-// path): the scalar-level stages of kernels/ed25519.hip alone, for
-// tests/test_gpu_ed_exact.py:
+// path): the stages of kernels/ed25519.hip alone, for
+// tests/test_gpu_ed_exact.py and tests/test_gpu_ed_point_exact.py:
 //   tk_ed_scalar : k = H mod L (ed_k_mod_l), the S check (ed_s_ok) and the
 //                  signed recoding (recode) of k at every key-table tier and
 //                  of S at the base-point width, per lane;
 //   tk_ed_finish : the production k_ed_finish at any tokens-per-thread B --
-//                  production picks B > 1 only from 262,144 padded tokens up.
+//                  production picks B > 1 only from 262,144 padded tokens up;
+//   tk_ed_point  : the production k_ed_point, k_ed_point_pf and
+//                  k_ed_point_split on sparse comb tables (tk_ed_point.hpp;
+//                  it lives in this translation unit because ed25519.hip
+//                  defines launch_ed and its kin, which one library holds once).
 // The verify chain only tells accept from reject, on SHA-random k.
 #include <hip/hip_runtime.h>
 
@@ -173,3 +177,5 @@ extern "C" int tk_ed_finish(int B, int64_t npad, int64_t begin, int64_t end, con
     if (ptr) (void)hipFree(ptr);
   return ok ? 0 : -2;
 }
+
+#include "tk_ed_point.hpp"

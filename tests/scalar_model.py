@@ -103,6 +103,25 @@ def ed_s_ok(sbytes):
     return (sbytes[31] & 0xE0) == 0 and int.from_bytes(sbytes, "little") < ED_L
 
 
+def ed_patterns(w):
+    """scalars below L whose windows at width w hit the recoding's edges"""
+    k = 252 // w                              # the highest window holding bits of a scalar < ED_L
+    sh, half, full = w * k, 1 << (w - 1), (1 << w) - 1
+    ntop = ED_L >> sh
+
+    def build(low, top):
+        u = sum(v << (w * i) for i, v in enumerate(low)) | (min(top, ntop - 1) << sh)
+        assert 0 < u < ED_L
+        return u
+
+    return [build([half - 1] * k, half - 1), build([half] * k, half), build([half + 1] * k, half + 1),
+            build([full] * k, ntop - 1),                                      # 2^252 - 1: a carry into a full top window
+            build([full] * (k - 1) + [half], ntop - 1),
+            build([(half + 1 if i % 2 else 0) for i in range(k)], 1),         # zero windows
+            (half + 1) << (w * (k // 2)), half << (w * (k // 2)),             # a lone digit
+            1, half, half + 1, ED_L - 1]
+
+
 def ed_encode(X, Y, Z):
     """canonical 32-byte encoding of the projective point (X : Y : Z), Z != 0 mod p"""
     zi = pow(Z % ED_P, -1, ED_P)

@@ -57,23 +57,7 @@ def _die_on_hip_error(rc, name):
 
 
 # ------------------------------------------------------------------ k, S, digits
-def ed_patterns(w):
-    """scalars below L whose windows at width w hit the recoding's edges"""
-    k = 252 // w                              # the highest window holding bits of a scalar < L
-    sh, half, full = w * k, 1 << (w - 1), (1 << w) - 1
-    ntop = L >> sh
-
-    def build(low, top):
-        u = sum(v << (w * i) for i, v in enumerate(low)) | (min(top, ntop - 1) << sh)
-        assert 0 < u < L
-        return u
-
-    return [build([half - 1] * k, half - 1), build([half] * k, half), build([half + 1] * k, half + 1),
-            build([full] * k, ntop - 1),                                      # 2^252 - 1: a carry into a full top window
-            build([full] * (k - 1) + [half], ntop - 1),
-            build([(half + 1 if i % 2 else 0) for i in range(k)], 1),         # zero windows
-            (half + 1) << (w * (k // 2)), half << (w * (k // 2)),             # a lone digit
-            1, half, half + 1, L - 1]
+ed_patterns = M.ed_patterns          # (tests/scalar_model.py: the CPU model tests use them too)
 
 
 def test_k_mod_l_s_check_and_recoding(tk):
